@@ -14,7 +14,7 @@ X-strips, one per GPU (strong scaling; goworld_amd/dworld.py over the
 library's gw_world_* path): each tick every rank routes its owned ops,
 exchanges halo rows with both neighbours (and far rows of long moves) over
 RCCL inside the library (xGMI) and ticks its strip; walkers cross borders.
-Two legs ride along in every N>1 line:
+Two legs ride along in every N>1 line of a --full run:
   "spaces": an independent 1M-entity config #3 space per GPU (seed 3 + rank),
   no data-path collective (weak scaling: a space never spans processes in the
   reference, engine/entity/SpaceManager.go:11-31, so that is how it shards);
@@ -30,7 +30,18 @@ Inputs (ops of every tick) are resident in HBM before the timed region;
 outputs stay in HBM (device-resident boundary); t_e2e reports the host-in /
 host-out tick separately.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+A plain run does only what the headline needs: load, W warm-up steps, the K
+timed steps, the result line (metric, value, unit, ms_per_step, ...).  --full
+adds everything else the line can carry: the HIP-event roofline of the
+dominant kernel and the per-stage breakdown, the end-to-end (host in / out)
+steps, the client-message ticks, the legs that ride along (config5, spaces,
+c3world) and the CPU baselines; the options that size or skip those parts
+(--profile-stages, --e2e-steps, --client-msgs, --no-config5, --no-spaces-leg,
+--no-c3world, --no-cpu-baseline, ...) act under --full only.
+--dump-outputs DIR writes what the last timed step returned to its caller
+(the tick's enter / leave events and the collect's sync records) as .npy files.
+
+Run:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
       (N>1 without torchrun: this process spawns the N rank processes itself,
       one per GPU, and never touches a GPU; rank 0 prints the line)
 N>1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
@@ -111,7 +122,20 @@ def parse():
                     help="extra untimed ticks measuring gw_client_events + gw_fanout (N=1 config #3; 0 = off)")
     ap.add_argument("--capacity", type=int, default=None,
                     help="slot capacity of the space (N=1: cost of a strip's id range at N ranks)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline and stage breakdown, end-to-end steps, client messages, "
+                         "the legs that ride along (config5 / spaces / c3world) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (enter / leave events, "
+                         "sync records, counts) to DIR/<name>.npy (N>1: <name>.rank<r>.npy per rank)")
+    a = ap.parse_args()
+    if a.dump_outputs and a.comm == "loopback" and a.gpus > 1:
+        ap.error("--dump-outputs: the loopback ranks share one process; dump a --gpus 1 or a multi-process run")
+    if not a.full:                                  # a plain run: the headline's own steps only
+        a.profile_stages = a.e2e_steps = a.client_msgs = 0
+        a.config5 = a.spaces_leg = a.c3world = False
+        a.no_cpu_baseline = True
+    return a
 
 
 class Ctl:
@@ -391,10 +415,11 @@ class SpaceRun:
         # all ticks' ops resident in HBM before timing
         self.m = len(self.tr.ticks[0])
         self.host_ticks = self.tr.ticks
-        ops_all = np.concatenate(self.tr.ticks)
-        self.dev_ops = g.dev_alloc(ops_all.nbytes)
-        g.h2d(self.dev_ops, ops_all)
         self.nbytes_tick = self.m * traces.OP_DTYPE.itemsize
+        assert all(len(ops) == self.m for ops in self.tr.ticks)
+        self.dev_ops = g.dev_alloc(self.nbytes_tick * max(len(self.tr.ticks), 1))
+        for t, ops in enumerate(self.tr.ticks):         # tick by tick: no second host copy of a long trace
+            g.h2d(self.dev_ops + t * self.nbytes_tick, ops)
         self.by_client = a.sync_by_client
         self.parallelism = f"independent spaces x{ctl.ws} (no comm)" if ctl.ws > 1 else "single GPU"
         self.n_world = self.tr.n * (ctl.ws if ctl.ws > 1 else 1)
@@ -707,10 +732,64 @@ def client_msgs(run, t0, n):
                       "of each; not part of ms_per_step"}
 
 
-def measure(run, a, ctl, warmup, steps, profile, extra):
+def read_outputs(g, r, s):
+    """What the caller of the last step received, copied from the device: the
+    tick's canonical enter / leave events and the collect's sync records
+    (device pointers and counts of gw_tick_out / gw_sync_out), in the
+    library's order."""
+    def pull(ptr, n, dtype):
+        arr = np.zeros(int(n), dtype)
+        if n:
+            g.d2h(arr, ptr)
+        return arr
+    return {"enter": pull(r.enter_dev, r.n_enter, gpuaoi.EVENT_DTYPE),
+            "leave": pull(r.leave_dev, r.n_leave, gpuaoi.EVENT_DTYPE),
+            "records": pull(s.rec_dev, s.n_rec, gpuaoi.REC_DTYPE)}
+
+
+DUMP_MAX_BYTES = 48 << 20     # of .npy data per rank; larger outputs are sampled (fixed seed)
+
+
+def dump_outputs(out, directory, rank, ws):
+    """read_outputs' arrays as DIR/<name>.npy: ids as float64 (u32 exact), the
+    records' payload as float32.  Past DUMP_MAX_BYTES the records (then the
+    events) are a seeded row sample, the same rows on every run of the same
+    shape; counts.npy holds the full lengths.  Returns {name: rows written}."""
+    os.makedirs(directory, exist_ok=True)
+    rows = {k: len(v) for k, v in out.items()}
+    cost = {"enter": 16, "leave": 16, "records": 32}          # bytes per row as written
+    budget = DUMP_MAX_BYTES
+    keep = {}
+    for i, k in enumerate(("enter", "leave", "records")):     # an equal share of what is left for each in turn
+        share = budget // (3 - i)
+        keep[k] = min(rows[k], share // cost[k])
+        budget -= keep[k] * cost[k]
+    rng = np.random.default_rng(0x5EED)
+    written = {}
+
+    def save(name, arr):
+        np.save(os.path.join(directory, name + (f".rank{rank}" if ws > 1 else "") + ".npy"), arr)
+        written[name] = len(arr)
+    for k in ("enter", "leave", "records"):
+        v = out[k]
+        if keep[k] < rows[k]:
+            v = v[np.sort(rng.choice(rows[k], keep[k], replace=False))]
+        if k == "records":
+            save("sync_ids", np.stack([v["watcher"], v["entity"]], axis=1).astype(np.float64))
+            save("sync_payload", np.stack([v["x"], v["y"], v["z"], v["yaw"]], axis=1).astype(np.float32))
+        else:
+            save(k, np.stack([v["watcher"], v["target"]], axis=1).astype(np.float64))
+    save("counts", np.array([rows["enter"], rows["leave"], rows["records"]], np.float64))
+    return written
+
+
+def measure(run, a, ctl, warmup, steps, profile, extra, dump=False):
     """W untimed steps, then exactly K steps bracketed by a barrier and a device
     sync on both sides; HIP events around the dominant kernel's stage in every
-    timed step; a per-stage breakdown over `extra` more untimed steps."""
+    timed step; a per-stage breakdown over `extra` more untimed steps.  dump:
+    the last timed step's outputs are read back after the timed region
+    (res["outputs"]); a replayed run then takes its last step as its own
+    gw_step call, which hands out the output structures."""
     g = run.g
     for t in range(warmup):
         run.step(t)
@@ -719,14 +798,16 @@ def measure(run, a, ctl, warmup, steps, profile, extra):
     ctl.barrier()
     g.synchronize()
     t0 = time.perf_counter()
-    if hasattr(run, "replay"):                  # the K steps as one gw_replay call
-        sm = run.replay(warmup, steps)
+    first, last = warmup, None
+    if hasattr(run, "replay"):                  # the K steps as one gw_replay call (dump: K - 1, then one gw_step)
+        first = warmup + (max(steps - 1, 0) if dump else steps)
+        sm = run.replay(warmup, first - warmup)
         ev = sm["n_enter"] + sm["n_leave"]
         tot.update(ops=sm["movers"], events=ev, records=sm["n_rec"], bytes_alg=sm["bytes_alg"],
                    mover_alg=4 * (sm["nbr_old"] + sm["nbr_new"]) + 8 * ev, events_alg=8 * ev,
                    sync_write_alg=24 * sm["n_rec"], cand=sm["pairs_tested"])
-    for t in range(warmup, warmup + steps) if not hasattr(run, "replay") else ():
-        upd, r, s = run.step(t)
+    for t in range(first, warmup + steps):
+        upd, r, s = last = run.step(t)
         ev = r.n_enter + r.n_leave
         tot["ops"] += upd
         tot["events"] += ev
@@ -743,6 +824,8 @@ def measure(run, a, ctl, warmup, steps, profile, extra):
     t1 = time.perf_counter()
     ctl.barrier()
     res = {"elapsed": t1 - t0, "tot": tot, "dom_us": None, "stages": {}}
+    if dump and last is not None:
+        res["outputs"] = read_outputs(g, last[1], last[2])
     if profile:
         for name, us, b, calls in g.stage_times():       # HIP events read back here, after the timed region
             if name == "diff":
@@ -867,7 +950,8 @@ def run(a, ctl):
         run = SpaceRun(a, ctl, ticks)
     t_load = time.perf_counter() - t_load
     g = run.g
-    res = measure(run, a, ctl, W, K, a.profile_stages, extra)
+    res = measure(run, a, ctl, W, K, a.profile_stages, extra, dump=bool(a.dump_outputs))
+    dumped = dump_outputs(res.pop("outputs"), a.dump_outputs, rank, ws) if "outputs" in res else None
     client = client_msgs(run, W + K + extra, cm) if cm else None
     e2e = {}
     if n_e2e >= 2:
@@ -1019,6 +1103,8 @@ def run(a, ctl):
     line.update(e2e)
     if e2e:
         line["t_device_ms_per_step"] = mx / K * 1e3
+    if dumped:
+        line["dumped_outputs"] = {"dir": a.dump_outputs, "rows": dumped}
     if client:
         line["client_msgs"] = client
     if loop:

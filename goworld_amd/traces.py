@@ -18,8 +18,11 @@ Sources of the workload shapes (reference paths):
 """
 from __future__ import annotations
 
+import collections
+import concurrent.futures
 import dataclasses
 import math
+import os
 
 import numpy as np
 
@@ -57,20 +60,57 @@ def stream_key(seed: int, *stream: int) -> np.uint64:
     return np.uint64(k)
 
 
+_COUNTERS: dict = {}       # n -> (1 .. n) * GOLDEN, the key-independent part of a stream's counters
+
+
+def _counters(n: int) -> np.ndarray:
+    c = _COUNTERS.get(n)
+    if c is None:
+        with np.errstate(over="ignore"):
+            c = np.arange(1, n + 1, dtype=np.uint64) * GOLDEN
+        if n <= (1 << 21):                    # kept for the sizes a trace draws every tick
+            if len(_COUNTERS) >= 8:
+                _COUNTERS.clear()
+            _COUNTERS[n] = c
+    return c
+
+
 def rand_u64(key, n: int, offset: int = 0) -> np.ndarray:
-    idx = np.arange(offset + 1, offset + n + 1, dtype=np.uint64)
+    """mix64(key + (offset + i + 1) * GOLDEN), i < n: one new array, mixed in
+    place (a long trace draws millions of these per tick)."""
     with np.errstate(over="ignore"):
-        return mix64(np.uint64(key) + idx * GOLDEN)
+        if offset:
+            z = np.arange(offset + 1, offset + n + 1, dtype=np.uint64) * GOLDEN
+            z += np.uint64(key)
+        else:
+            z = _counters(n) + np.uint64(key)
+        t = z >> np.uint64(30)
+        z ^= t
+        z *= _M1
+        np.right_shift(z, np.uint64(27), out=t)
+        z ^= t
+        z *= _M2
+        np.right_shift(z, np.uint64(31), out=t)
+        z ^= t
+    return z
 
 
 def rand_unit(key, n: int) -> np.ndarray:
     """Uniform float64 in [0, 1)."""
-    return (rand_u64(key, n) >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+    u = rand_u64(key, n)
+    u >>= np.uint64(11)
+    f = u.astype(np.float64)
+    f *= 1.0 / 9007199254740992.0
+    return f
 
 
 def rand_f32(key, n: int) -> np.ndarray:
     """Uniform float32 in [0, 1) with 24 random bits (like Go rand.Float32)."""
-    return ((rand_u64(key, n) >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0))
+    u = rand_u64(key, n)
+    u >>= np.uint64(40)
+    f = u.astype(np.float32)
+    f *= np.float32(1.0 / 16777216.0)
+    return f
 
 
 def rand_int(key, n: int, lo: int, hi: int) -> np.ndarray:
@@ -111,6 +151,19 @@ def _choose_movers(key, n: int, m: int) -> np.ndarray:
     r = rand_u64(key, n)
     if m >= n:
         return np.argsort(r, kind="stable").astype(np.uint32)
+    if n >= (1 << 16) and m > 0:
+        # the m smallest of n uniform 64-bit draws lie under a bound a few
+        # standard deviations past the m/n quantile: sort those alone
+        bound = (m + 8.0 * math.sqrt(m) + 8.0) / n
+        if bound < 0.5:
+            part = np.flatnonzero(r < np.uint64(int(bound * 2.0 ** 64)))
+            if len(part) >= m:
+                v = r[part]
+                order = np.argsort(v)                 # distinct keys sort alike under any algorithm
+                sv = v[order]
+                if (sv[1:] == sv[:-1]).any():
+                    order = np.argsort(v, kind="stable")
+                return part[order[:m]].astype(np.uint32)
     part = np.argpartition(r, m - 1)[:m]
     return part[np.argsort(r[part], kind="stable")].astype(np.uint32)
 
@@ -163,14 +216,17 @@ def dyadic_walk_trace(seed: int, n: int, side: float, d: float, ticks: int,
     gates[:n] = np.where(has_client, gsel, 0)
     tr.gates = gates
     m = int(round(n * move_frac))
-    for t in range(ticks):
+
+    def draws(t):
+        """Tick t's draws, none of which depends on the walk's state (every
+        stream is keyed by (seed, stream, t)): the movers, their steps and
+        yaws, and the ops but for the positions."""
         movers = _choose_movers(stream_key(seed, 100, t), n, m)
-        sq = np.where(is_hot[movers], hot_step_q, step_q)
+        idx = movers.astype(np.intp)
+        sq = np.where(is_hot[idx], hot_step_q, step_q)
         dx = (rand_unit(stream_key(seed, 101, t), m) * (2 * sq + 1)).astype(np.int64) - sq
         dz = (rand_unit(stream_key(seed, 102, t), m) * (2 * sq + 1)).astype(np.int64) - sq
-        kx[movers] = _reflect_q(kx[movers] + dx, lo_q, hi_q)
-        kz[movers] = _reflect_q(kz[movers] + dz, zlo_q, zhi_q)
-        yaw[movers] = rand_f32(stream_key(seed, 103, t), m) * np.float32(2 * math.pi)
+        new_yaw = rand_f32(stream_key(seed, 103, t), m) * np.float32(2 * math.pi)
         from_client = rand_unit(stream_key(seed, 104, t), m) < 0.5
         ops = make_ops(m)
         ops["kind"] = OP_MOVED
@@ -178,11 +234,86 @@ def dyadic_walk_trace(seed: int, n: int, side: float, d: float, ticks: int,
         # from the client (Entity.go:1199-1204)
         ops["sync_flags"] = np.where(from_client, SIF_NEIGHBOR, SIF_NEIGHBOR | SIF_OWN)
         ops["slot"] = movers
-        ops["x"] = (kx[movers] / Q).astype(np.float32)
-        ops["z"] = (kz[movers] / Q).astype(np.float32)
-        ops["yaw"] = yaw[movers]
-        tr.ticks.append(ops)
+        ops["yaw"] = new_yaw
+        return idx, dx, dz, new_yaw, ops
+
+    def axis(k, lo, hi, field):
+        """One axis of the walk (positions of tick t from those of tick t - 1)."""
+        def step(idx, dk, ops):
+            nk = k[idx]
+            nk += dk
+            out = np.flatnonzero((nk < lo) | (nk >= hi))
+            if len(out):
+                nk[out] = _reflect_q(nk[out], lo, hi)
+            k[idx] = nk                                  # the movers of a tick are distinct
+            ops[field] = (nk / Q).astype(np.float32)
+        return step
+
+    # the walk is serial from tick to tick, but x, z and yaw walk on their own
+    threads = _threads(ticks, n)
+    lanes = _Lanes(3, threads)
+    step_x, step_z = axis(kx, lo_q, hi_q, "x"), axis(kz, zlo_q, zhi_q, "z")
+    try:
+        for idx, dx, dz, new_yaw, ops in _map_ahead(draws, ticks, threads):
+            lanes.submit(0, step_x, idx, dx, ops)
+            lanes.submit(1, step_z, idx, dz, ops)
+            lanes.submit(2, yaw.__setitem__, idx, new_yaw)
+            tr.ticks.append(ops)
+    finally:
+        lanes.finish()
     return tr
+
+
+def _threads(count: int, n: int) -> int:
+    """Threads for a trace of `count` ticks over n entities: a long trace of a
+    large population spends its time in numpy passes that release the GIL."""
+    workers = min(16, os.cpu_count() or 1)
+    return workers if (workers >= 2 and count >= 2 and n >= (1 << 16)) else 0
+
+
+def _map_ahead(fn, count: int, threads: int):
+    """fn(0), fn(1), ... fn(count - 1) in order; with threads, the calls run a
+    few ticks ahead on a pool.  The results are the same either way."""
+    if not threads:
+        for t in range(count):
+            yield fn(t)
+        return
+    with concurrent.futures.ThreadPoolExecutor(threads) as pool:
+        ahead = collections.deque(pool.submit(fn, t) for t in range(min(2 * threads, count)))
+        nxt = len(ahead)
+        while ahead:
+            res = ahead.popleft().result()
+            if nxt < count:
+                ahead.append(pool.submit(fn, nxt))
+                nxt += 1
+            yield res
+
+
+class _Lanes:
+    """Chains of calls, serial within a chain and independent between chains:
+    with threads, chain i runs on a thread of its own in submission order,
+    at most `depth` calls behind the submitter; else submit() calls at once."""
+
+    def __init__(self, k: int, threads: int, depth: int = 96):
+        self.pools = [concurrent.futures.ThreadPoolExecutor(1) for _ in range(k)] if threads else None
+        self.pending = collections.deque()
+        self.depth = depth
+
+    def submit(self, i: int, fn, *args):
+        if self.pools is None:
+            fn(*args)
+            return
+        self.pending.append(self.pools[i].submit(fn, *args))
+        if len(self.pending) > self.depth:
+            self.pending.popleft().result()
+
+    def finish(self):
+        try:
+            while self.pending:
+                self.pending.popleft().result()
+        finally:
+            for p in self.pools or ():
+                p.shutdown()
 
 
 def config2(ticks: int = 100, seed: int = 2, n: int = 100_000) -> SpaceTrace:

@@ -61,7 +61,7 @@ def test_torchrun_ranks():
     assert line["n_gpus"] == 2 and line["ranks_reporting"] == 2
 
 
-_SMALL = ["--entities", "100000", "--steps", "3", "--warmup", "2", "--no-config5", "--no-cpu-baseline",
+_SMALL = ["--full", "--entities", "100000", "--steps", "3", "--warmup", "2", "--no-config5", "--no-cpu-baseline",
           "--profile-stages", "0", "--client-msgs", "0", "--e2e-steps", "0"]
 
 
@@ -97,3 +97,103 @@ def test_bench_loopback_world_line():
     line = _line(p.stdout)
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["value"] > 0
     assert line["spaces"]["scaling"] == "weak" and line["spaces"]["value"] > 0
+
+
+def _parse(monkeypatch, *argv):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    return bench.parse()
+
+
+def test_plain_run_measures_the_headline_only(monkeypatch):
+    """Without --full nothing but the headline's steps is switched on, whatever
+    the part options say; --full restores every part at its default."""
+    for argv in (["--gpus", "1", "--steps", "7", "--warmup", "2"], ["--e2e-steps", "8", "--client-msgs", "5"]):
+        a = _parse(monkeypatch, *argv)
+        assert not a.full and a.no_cpu_baseline
+        assert a.profile_stages == 0 and a.e2e_steps == 0 and a.client_msgs == 0
+        assert not (a.config5 or a.spaces_leg or a.c3world)
+    assert (a.steps, a.warmup) == (20, 30)
+    a = _parse(monkeypatch, "--full", "--steps", "7")
+    assert a.full and a.steps == 7 and not a.no_cpu_baseline
+    assert a.profile_stages == 1 and a.e2e_steps == 8 and a.client_msgs == 5
+    assert a.config5 and a.spaces_leg and a.c3world
+    assert not _parse(monkeypatch, "--full", "--no-config5", "--client-msgs", "0").config5
+
+
+def test_dump_outputs_files(tmp_path):
+    """dump_outputs: float32 / float64 .npy files, exact ids, the full lengths
+    in counts.npy, and past the size cap the same seeded rows on every call."""
+    import numpy as np
+    import bench
+    from goworld_amd import gpuaoi
+    n = bench.DUMP_MAX_BYTES // 32 + 1000          # records alone pass the cap
+    rec = np.zeros(n, gpuaoi.REC_DTYPE)
+    rec["watcher"] = np.arange(n, dtype=np.uint32)[::-1] + np.uint32(2 ** 32 - n)
+    rec["entity"] = np.arange(n)
+    rec["x"] = np.arange(n) * np.float32(0.5)
+    ev = np.zeros(5, gpuaoi.EVENT_DTYPE)
+    ev["watcher"], ev["target"] = np.arange(5), 4_000_000_000 + np.arange(5)
+    out = {"enter": ev, "leave": ev[:0], "records": rec}
+    rows = bench.dump_outputs(out, str(tmp_path / "a"), 0, 1)
+    assert bench.dump_outputs(out, str(tmp_path / "b"), 0, 1) == rows
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["counts.npy", "enter.npy", "leave.npy", "sync_ids.npy", "sync_payload.npy"]
+    arr = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    assert all(v.dtype in (np.float32, np.float64) for v in arr.values())
+    assert arr["counts"].tolist() == [5, 0, n]
+    assert np.array_equal(arr["enter"], np.stack([ev["watcher"], ev["target"]], 1).astype(np.float64))
+    assert arr["leave"].shape == (0, 2)
+    k = rows["sync_ids"]
+    assert 0 < k < n and arr["sync_ids"].shape == (k, 2) and arr["sync_payload"].shape == (k, 4)
+    idx = arr["sync_ids"][:, 1].astype(np.int64)           # entity = the row's index: a sorted sample of rows
+    assert np.all(np.diff(idx) > 0)
+    assert np.array_equal(arr["sync_ids"][:, 0], rec["watcher"][idx].astype(np.float64))
+    assert np.array_equal(arr["sync_payload"][:, 0], rec["x"][idx])
+    for f in files:
+        assert np.array_equal(arr[f[:-4]], np.load(tmp_path / "b" / f))
+    assert sorted(os.listdir(tmp_path / "b")) == files
+    bench.dump_outputs(out, str(tmp_path / "a"), 1, 2)
+    assert "enter.rank1.npy" in os.listdir(tmp_path / "a")
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """A plain run prints the headline without the parts behind --full, and
+    --dump-outputs holds what the last of the K timed steps returns: the
+    events and records of tick W + K - 1 of the same trace stepped through
+    gw_submit / gw_tick / gw_sync_collect here (events in the canonical
+    order; records as a multiset: the two call paths may order them apart)."""
+    import numpy as np
+    from goworld_amd import gpuaoi, traces
+    n, W, K = 50_000, 2, 3
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--entities",
+                        str(n), "--dump-outputs", str(tmp_path)], cwd=ROOT, env=_env(), capture_output=True,
+                       text=True, timeout=110)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = _line(p.stdout)
+    assert line["steps"] == K and line["warmup"] == W and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "updates/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    for part in ("cpu_baseline", "cpu_baseline_mt", "config5", "t_e2e", "t_e2e_wire", "client_msgs", "stages"):
+        assert part not in line
+    assert line["roofline"] is None
+    tr = traces.config3(ticks=W + K, seed=3, n=n)
+    with gpuaoi.GpuAOI(0) as g:
+        gpuaoi.load_space(g, tr)
+        g.sync_collect(copy=False)
+        for ops in tr.ticks:
+            g.submit(ops)
+            r = g.tick()
+            s = g.sync_collect()
+    got = {f: np.load(tmp_path / (f + ".npy")) for f in ("counts", "enter", "leave", "sync_ids", "sync_payload")}
+    assert got["counts"].tolist() == [r.n_enter, r.n_leave, s.n_rec] and r.n_enter > 0 and s.n_rec > 0
+    assert line["dumped_outputs"]["rows"]["sync_ids"] == s.n_rec
+    for name, ev in (("enter", r.enter), ("leave", r.leave)):
+        assert np.array_equal(got[name], np.stack([ev["watcher"], ev["target"]], 1).astype(np.float64))
+    rec = s.records
+    want = np.concatenate([np.stack([rec["watcher"], rec["entity"]], 1).astype(np.float64),
+                           np.stack([rec["x"], rec["y"], rec["z"], rec["yaw"]], 1).astype(np.float64)], 1)
+    have = np.concatenate([got["sync_ids"], got["sync_payload"].astype(np.float64)], 1)
+    assert got["sync_payload"].dtype == np.float32 and got["sync_ids"].dtype == np.float64
+    assert np.array_equal(have[np.lexsort(have.T[::-1])], want[np.lexsort(want.T[::-1])])

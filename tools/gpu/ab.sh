@@ -3,7 +3,7 @@
 set -o pipefail
 tag=$1; shift
 mkdir -p gpurun_out
-B="--no-cpu-baseline --no-config5 --e2e-steps 0 --client-msgs 0"
+B="--full --no-cpu-baseline --no-config5 --e2e-steps 0 --client-msgs 0"
 show() { python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); s=d.get('stages',{}); print(sys.argv[2], round(d['ms_per_step'],4), {k: v['avg_us'] for k, v in s.items()})" "$1" "$2"; }
 i=0
 for spec in "$@"; do

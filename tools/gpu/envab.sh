@@ -6,7 +6,7 @@ tag=$1; cfg=$2; shift 2
 specs=(); extra=()
 while [ $# -gt 0 ]; do if [ "$1" = "--" ]; then shift; extra=("$@"); break; fi; specs+=("$1"); shift; done
 mkdir -p gpurun_out
-B="--no-cpu-baseline --no-config5 --e2e-steps 0 --client-msgs 0"
+B="--full --no-cpu-baseline --no-config5 --e2e-steps 0 --client-msgs 0"
 show() { python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); s=d.get('stages',{}); print(sys.argv[2], round(d['ms_per_step'],4), {k: v['avg_us'] for k, v in s.items()})" "$1" "$2"; }
 for rep in 1 2; do
   i=0

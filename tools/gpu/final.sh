@@ -19,9 +19,11 @@ bash tools/gpu/pmc.sh ${tag}c4 4 > gpurun_out/pmc_${tag}c4.log 2>&1 || { tail -2
 cp gpurun_out/pmc_${tag}c4/pmc_config4.json profiles/pmc_config4.json
 fi
 [[ $phase == *b* ]] || exit 0
-timeout -k 10 480 python -u bench.py > gpurun_out/bench_$tag.json.log 2>&1 || { tail -20 gpurun_out/bench_$tag.json.log; exit 1; }
-tail -1 gpurun_out/bench_$tag.json.log | cut -c1-400
-timeout -k 10 420 python -u bench.py --config 4 --no-cpu-baseline --no-config5 --client-msgs 0 > gpurun_out/bench_${tag}_c4.json.log 2>&1 || { tail -20 gpurun_out/bench_${tag}_c4.json.log; exit 1; }
+# the bench lines go to $GW_OUT (default bench_out/), where keep_evidence.sh looks for them
+out=${GW_OUT:-bench_out}; mkdir -p $out
+timeout -k 10 480 python -u bench.py --full > $out/bench_$tag.json.log 2>&1 || { tail -20 $out/bench_$tag.json.log; exit 1; }
+tail -1 $out/bench_$tag.json.log | cut -c1-400
+timeout -k 10 420 python -u bench.py --full --config 4 --no-cpu-baseline --no-config5 --client-msgs 0 > $out/bench_${tag}_c4.json.log 2>&1 || { tail -20 $out/bench_${tag}_c4.json.log; exit 1; }
 bash tools/gpu/prof.sh $tag > /dev/null && head -8 gpurun_out/prof_${tag}_per_step.txt || exit 1
 bash tools/gpu/prof.sh ${tag}c4 --config 4 > /dev/null && head -8 gpurun_out/prof_${tag}c4_per_step.txt || exit 1
 bash tools/gpu/fprof.sh $tag > gpurun_out/fprof_$tag.txt 2>&1 || { tail -20 gpurun_out/fprof_$tag.txt; exit 1; }

@@ -5,7 +5,7 @@ set -o pipefail
 tag=${1:-cur}
 mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-B="--no-cpu-baseline --profile-stages 0 --e2e-steps 0 --no-config5"
+B="--full --no-cpu-baseline --profile-stages 0 --e2e-steps 0 --no-config5"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/fprof_${tag}_msgs -o run -- python3 bench.py $B --steps 2 --warmup 3 --client-msgs 5 > gpurun_out/fprof_${tag}_msgs.log 2>&1 || { tail -20 gpurun_out/fprof_${tag}_msgs.log; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/fprof_${tag}_bycl -o run -- python3 bench.py $B --steps 5 --warmup 3 --client-msgs 0 --sync-by-client > gpurun_out/fprof_${tag}_bycl.log 2>&1 || { tail -20 gpurun_out/fprof_${tag}_bycl.log; exit 1; }
 for w in msgs bycl; do

@@ -9,8 +9,9 @@ for i in 1 2 3 4; do
   [ -f gpurun_out/pmc_$tag/p$i.txt ] && cp gpurun_out/pmc_$tag/p$i.txt profiles/${pre}_pmc_p$i.txt
   [ -f gpurun_out/pmc_${tag}c4/p$i.txt ] && cp gpurun_out/pmc_${tag}c4/p$i.txt profiles/${pre}_config4_pmc_p$i.txt
 done
-[ -f gpurun_out/bench_$tag.json.log ] && tail -1 gpurun_out/bench_$tag.json.log > profiles/${pre}_bench.json
-[ -f gpurun_out/bench_${tag}_c4.json.log ] && tail -1 gpurun_out/bench_${tag}_c4.json.log > profiles/${pre}_config4_bench.json
+out=${GW_OUT:-bench_out}          # where final.sh put the bench lines
+[ -f $out/bench_$tag.json.log ] && tail -1 $out/bench_$tag.json.log > profiles/${pre}_bench.json
+[ -f $out/bench_${tag}_c4.json.log ] && tail -1 $out/bench_${tag}_c4.json.log > profiles/${pre}_config4_bench.json
 for s in "" c4; do
   [ -f gpurun_out/prof_${tag}${s}_per_step.txt ] && cp gpurun_out/prof_${tag}${s}_per_step.txt profiles/${pre}${s:+_config4}_per_step.txt
   [ -f gpurun_out/prof_${tag}${s}_kernel_stats.csv ] && cp gpurun_out/prof_${tag}${s}_kernel_stats.csv profiles/${pre}${s:+_config4}_kernel_stats.csv
