@@ -2250,7 +2250,9 @@ void launch_bk_split_init(uint32_t* sp, int wbits, hipStream_t s) {
     hipLaunchKernelGGL(k_bk_split_init, dim3(1), dim3(NT), 0, s, sp, wbits);
 }
 
-void tick_diff(const TickBufs& b, hipStream_t s) {
+// Returns the name of the diff kernel it launched (GW_DEBUG_STATS prints it):
+// each token stands beside its launch, so it cannot drift from the dispatch.
+const char* tick_diff(const TickBufs& b, hipStream_t s) {
     const uint64_t nmax = 2ull * b.m;
     if (b.small_ents) {                    // small-space mode: a block per space
         const size_t lds = ((size_t)b.small_ents + (2 * ((size_t)b.small_cells + 1) + 3) / 4) * 16 +
@@ -2258,34 +2260,34 @@ void tick_diff(const TickBufs& b, hipStream_t s) {
         if (b.small_halves) {
             hipLaunchKernelGGL((k_mover_small<2, true>), dim3(b.n_spaces), dim3(NT), lds, s, b);
             hipLaunchKernelGGL((k_mover_list<2>), dim3(std::min<uint32_t>(nblk1(nmax, 1), 1024)), dim3(64), 0, s, b);
-        } else {
-            hipLaunchKernelGGL((k_mover_small<2, false>), dim3(b.n_spaces), dim3(NT), lds, s, b);
+            return "k_mover_small<2,1>";
         }
-        return;
+        hipLaunchKernelGGL((k_mover_small<2, false>), dim3(b.n_spaces), dim3(NT), lds, s, b);
+        return "k_mover_small<2,0>";
     }
     if (b.pair_max) {                      // two short-list movers per wave (GW_PAIR_MAX, 0 = off)
         hipLaunchKernelGGL((k_mover_pair<2>), dim3(nblk1(nmax, 2)), dim3(64), 0, s, b);
-        return;
+        return "k_mover_pair<2>";
     }
     if (b.compact) {                       // one wave per primary entry (<= one per op)
         const dim3 g(nblk1(b.m, 1));
         // gate words: 0, or 2 (<= 8 gate ids) / 4 per lane for the split by gate
         const int gw = b.gate_counts ? (b.gate_counts <= 8 ? 2 : 4) : 0;
         if (std::isinf(b.long_step)) {     // no long movers: the group-teleport paths compiled out
-            if (gw == 2) hipLaunchKernelGGL((k_mover_c<2, false, 2>), g, dim3(64), 0, s, b);
-            else if (gw == 4) hipLaunchKernelGGL((k_mover_c<2, false, 4>), g, dim3(64), 0, s, b);
-            else hipLaunchKernelGGL((k_mover_c<2, false, 0>), g, dim3(64), 0, s, b);
-        } else {
-            if (gw == 2) hipLaunchKernelGGL((k_mover_c<2, true, 2>), g, dim3(64), 0, s, b);
-            else if (gw == 4) hipLaunchKernelGGL((k_mover_c<2, true, 4>), g, dim3(64), 0, s, b);
-            else hipLaunchKernelGGL((k_mover_c<2, true, 0>), g, dim3(64), 0, s, b);
+            if (gw == 2) { hipLaunchKernelGGL((k_mover_c<2, false, 2>), g, dim3(64), 0, s, b); return "k_mover_c<2,0,2>"; }
+            if (gw == 4) { hipLaunchKernelGGL((k_mover_c<2, false, 4>), g, dim3(64), 0, s, b); return "k_mover_c<2,0,4>"; }
+            hipLaunchKernelGGL((k_mover_c<2, false, 0>), g, dim3(64), 0, s, b);
+            return "k_mover_c<2,0,0>";
         }
-        return;
+        if (gw == 2) { hipLaunchKernelGGL((k_mover_c<2, true, 2>), g, dim3(64), 0, s, b); return "k_mover_c<2,1,2>"; }
+        if (gw == 4) { hipLaunchKernelGGL((k_mover_c<2, true, 4>), g, dim3(64), 0, s, b); return "k_mover_c<2,1,4>"; }
+        hipLaunchKernelGGL((k_mover_c<2, true, 0>), g, dim3(64), 0, s, b);
+        return "k_mover_c<2,1,0>";
     }
     switch (b.diff_u) {                    // GW_MOVER_WPB: waves per k_mover block
-    case 2: hipLaunchKernelGGL((k_mover<2, 2>), dim3(nblk1(nmax, 2)), dim3(128), 0, s, b); break;
-    case 4: hipLaunchKernelGGL((k_mover<2, 4>), dim3(nblk1(nmax, 4)), dim3(256), 0, s, b); break;
-    default: hipLaunchKernelGGL((k_mover<2, 1>), dim3(nblk1(nmax, 1)), dim3(64), 0, s, b); break;
+    case 2: hipLaunchKernelGGL((k_mover<2, 2>), dim3(nblk1(nmax, 2)), dim3(128), 0, s, b); return "k_mover<2,2>";
+    case 4: hipLaunchKernelGGL((k_mover<2, 4>), dim3(nblk1(nmax, 4)), dim3(256), 0, s, b); return "k_mover<2,4>";
+    default: hipLaunchKernelGGL((k_mover<2, 1>), dim3(nblk1(nmax, 1)), dim3(64), 0, s, b); return "k_mover<2,1>";
     }
 }
 void tick_events(const TickBufs& b, ScanCtx& sc, hipStream_t s) {

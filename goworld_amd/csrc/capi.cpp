@@ -559,7 +559,8 @@ int gw_init(int device_id, gw_ctx** out) {
         if (const char* e = getenv("GW_MOVER_WPB")) c->diff_u = atoi(e);
         if (const char* e = getenv("GW_NB_U")) c->nb_u = atoi(e);
         if (const char* e = getenv("GW_WALK_MIN")) c->walk_min = (uint32_t)std::max(0, atoi(e));
-        if (const char* e = getenv("GW_RANK_SORT")) c->rank_sort = (uint32_t)std::max(0, atoi(e));
+        // (the rank placement reads lanes 0..n-1 of one wave: at most 64)
+        if (const char* e = getenv("GW_RANK_SORT")) c->rank_sort = (uint32_t)std::min(64, std::max(0, atoi(e)));
         if (const char* e = getenv("GW_GRID_CAP")) c->grid_cap = (uint32_t)std::max(0, atoi(e));
         if (const char* e = getenv("GW_PAIR_AUTO")) c->pair_auto = atoi(e) != 0;
         if (const char* e = getenv("GW_PAIR_MAX")) {
@@ -572,6 +573,12 @@ int gw_init(int device_id, gw_ctx** out) {
         if (const char* e = getenv("GW_DIRTY_SPAN")) c->dirty_span = (uint32_t)std::min(64, std::max(1, atoi(e)));
         if (const char* e = getenv("GW_HALF_ROWS")) c->half_rows = (uint32_t)std::min(16, std::max(0, atoi(e)));
         if (const char* e = getenv("GW_GATE_LANE_MAX")) c->gate_lane_max = (uint32_t)std::min(255, std::max(0, atoi(e)));
+        if (const char* e = getenv("GW_SMALL")) c->small_on = atoi(e) != 0;
+        if (const char* e = getenv("GW_MOVER_HALVES")) c->mover_halves = atoi(e) != 0;
+        if (const char* e = getenv("GW_SYNC_HALVES")) c->sync_halves = atoi(e) != 0;
+        if (const char* e = getenv("GW_GATE_COUNTS")) c->gate_counts_on = atoi(e) != 0;
+        if (const char* e = getenv("GW_GATE_DIRECT")) c->gate_direct_on = atoi(e) != 0;
+        c->debug_stats = getenv("GW_DEBUG_STATS") != nullptr;
     } while (0);
     if (rc) {
         (void)hipGetLastError();
@@ -1039,13 +1046,11 @@ static void small_mode(gw_ctx* c, TickBufs& b) {
             me = std::max(me, sp.cap);
             mc = std::max(mc, (uint32_t)(sp.p.W * sp.p.H));
         }
-    static const bool on = !getenv("GW_SMALL") || atoi(getenv("GW_SMALL")) != 0;
     b.n_spaces = (uint32_t)c->spaces.size();
-    const bool small = on && b.n_spaces >= 2 && (size_t)me * sizeof(GEnt) + 2 * ((size_t)mc + 1) * 4 <= SMALL_LDS_MAX;
+    const bool small = c->small_on && b.n_spaces >= 2 && (size_t)me * sizeof(GEnt) + 2 * ((size_t)mc + 1) * 4 <= SMALL_LDS_MAX;
     b.small_ents = small ? me : 0;
     b.small_cells = small ? mc : 0;
-    static const bool halves = !getenv("GW_MOVER_HALVES") || atoi(getenv("GW_MOVER_HALVES")) != 0;
-    b.small_halves = halves ? 1 : 0;
+    b.small_halves = c->mover_halves ? 1 : 0;
 }
 
 static void bind_events(gw_ctx* c, TickBufs& b) {
@@ -1110,7 +1115,7 @@ static int finish_tick(gw_ctx* c, gw_tick_out* out) {
                 if (f != SH_MOVERS || i) h->shard[i][f] = 0;
         HIPCHK(hipMemcpyAsync(c->stats, c->hstats, sizeof(DevStats), hipMemcpyHostToDevice, c->st));
         prof_begin(c, "diff");
-        tick_diff(b, c->st);
+        c->diff_variant = tick_diff(b, c->st);       // the line below names the final attempt's kernel
         s_diff = prof_end(c, 0);
         prof_begin(c, "events");
         tick_events(b, c->sc, c->st);
@@ -1150,14 +1155,15 @@ static int finish_tick(gw_ctx* c, gw_tick_out* out) {
     uint64_t a_old = 0, a_new = 0;
     a_old = hs.shard[0][SH_AOLD] & 0xffffffffull;
     a_new = hs.shard[0][SH_AOLD] >> 32;
-    if (getenv("GW_DEBUG_STATS")) {
+    if (c->debug_stats) {
         unsigned long long f0 = 0, f2 = 0;
         f0 = hs.shard[0][0];
         f2 = hs.shard[0][2];
         fprintf(stderr, "gw_tick: movers %llu gm %llu cand %llu ev %llu+%llu big %llu mlist %llu "
-                "f0 %llu f2 %llu bits %d full %d items %llu\n",
+                "f0 %llu f2 %llu bits %d full %d items %llu heavy %llu diff=%s rank=%d\n",
                 (unsigned long long)n_mov, hs.n_gm, hs.cand_total & CAND_MASK, hs.ev_pk & 0xffffffffull,
-                hs.ev_pk >> 32, hs.n_big, hs.n_mlist, f0, f2, b.bk_bits, b.ev_full, hs.n_items);
+                hs.ev_pk >> 32, hs.n_big, hs.n_mlist, f0, f2, b.bk_bits, b.ev_full, hs.n_items, hs.n_heavy,
+                flags & GW_TICK_NO_EVENTS ? "none" : c->diff_variant, c->c_rank);
     }
     o.ops = M;
     o.movers = n_mov;
@@ -1362,8 +1368,7 @@ int gw_tick(gw_ctx* c, uint32_t flags, gw_tick_out* out) {
     b.n_long = c->wd.tick_nlong;
     b.conflicts = c->wd.on ? &st->n_conflicts : nullptr;   // per attempt: a redo must not count twice
     // (the multi-gate collect; GW_GATE_COUNTS=0: its count pass walks every window, A/B)
-    static const bool gcounts_on = !getenv("GW_GATE_COUNTS") || atoi(getenv("GW_GATE_COUNTS")) != 0;
-    b.gate_counts = (gcounts_on && c->max_gate + 1u > 2u && c->max_gate + 1u <= GATE_DIRECT_MAX) ? c->max_gate + 1u : 0u;
+    b.gate_counts = (c->gate_counts_on && c->max_gate + 1u > 2u && c->max_gate + 1u <= GATE_DIRECT_MAX) ? c->max_gate + 1u : 0u;
     c->wd.tick_longs = nullptr;
     c->wd.tick_nlong = 0;
     b.ol = c->ol;
@@ -1422,7 +1427,7 @@ int gw_tick(gw_ctx* c, uint32_t flags, gw_tick_out* out) {
     if (ev_on) tick_movers(b, c->sc, c->st, dirty_later ? &bg : nullptr);
     size_t s_movers = prof_end(c, 0);
     prof_begin(c, "diff");
-    if (ev_on) tick_diff(b, c->st);
+    c->diff_variant = ev_on ? tick_diff(b, c->st) : "none";
     size_t s_diff = prof_end(c, 0);
     HIPCHK(hipEventRecord(c->ev_diff, c->st));        // a following collect may start here (st2)
     prof_begin(c, "events");
@@ -1486,8 +1491,7 @@ int gw_sync_collect(gw_ctx* c, uint32_t flags, gw_sync_out* out) {
             max_cells = std::max(max_cells, (uint32_t)(sp.p.W * sp.p.H));
         }
     const uint32_t n_sp = (uint32_t)c->spaces.size();
-    static const bool small_on = !getenv("GW_SMALL") || atoi(getenv("GW_SMALL")) != 0;
-    const bool small = small_on && n_sp >= 2 &&
+    const bool small = c->small_on && n_sp >= 2 &&
                        (size_t)max_ents * sizeof(GEnt) + ((size_t)max_cells + 1) * 4 <= SMALL_LDS_MAX;
     // the spaces' runs of the flagged list: zeroed by the compaction, set by the count pass
     if (small && (rc = ensure(c, c->srange, (size_t)n_sp * 8))) return rc;
@@ -1501,8 +1505,7 @@ int gw_sync_collect(gw_ctx* c, uint32_t flags, gw_sync_out* out) {
     const bool by_client = (flags & GW_SYNC_BY_CLIENT) != 0;
     // several gate ids in use: records straight into their gates' partitions
     // (counts and offsets per (gate, entry), gate-major; sync.hip)
-    static const bool gdirect_on = !getenv("GW_GATE_DIRECT") || atoi(getenv("GW_GATE_DIRECT")) != 0;
-    const bool gdirect = gdirect_on && G > 2 && G <= GATE_DIRECT_MAX && !by_client && !small;
+    const bool gdirect = c->gate_direct_on && G > 2 && G <= GATE_DIRECT_MAX && !by_client && !small;
     const uint64_t NG = gdirect ? (uint64_t)G * NFM : NFM;   // count / offset entries
     if (gdirect && ((rc = ensure(c, c->rec_cnt, NG * 4)) || (rc = ensure(c, c->rec_off, NG * 8)) ||
                     (rc = ensure_scan(c, NG))))
@@ -1543,19 +1546,23 @@ int gw_sync_collect(gw_ctx* c, uint32_t flags, gw_sync_out* out) {
     // short lists two per wave when the last collect averaged <= 64 records per
     // flagged entity (config #5: write 1081 -> 852 us; config #3's 146: +4 us)
     const bool sw_halves = c->sw_halves < 0 ? c->rec_per_flagged <= 64.0 : c->sw_halves > 0;
+    const char* write_variant = "none";                  // the kernel of the last write pass (debug_stats)
     auto write_pass = [&](hipStream_t ws) {
         if (gdirect)
-            launch_sync_write_gates(w, P<uint32_t>(c->flagged), P<uint32_t>(c->fbits), nf, NFM, G,
-                                    P<uint64_t>(c->rec_off), P<gw_sync_record>(c->rec0), c->rec_cap, st, ws);
+            write_variant = launch_sync_write_gates(w, P<uint32_t>(c->flagged), P<uint32_t>(c->fbits), nf, NFM, G,
+                                                    P<uint64_t>(c->rec_off), P<gw_sync_record>(c->rec0), c->rec_cap,
+                                                    st, ws);
         else if (small)
-            launch_sync_write_small(w, n_sp, P<uint32_t>(c->flagged), P<uint32_t>(c->fbits), P<uint64_t>(c->rec_off),
-                                    P<uint32_t>(c->rec_cnt), P<gw_sync_record>(c->rec0), c->rec_cap, st,
-                                    sfirst, slast, max_ents, max_cells, ws);
+            write_variant = launch_sync_write_small(w, n_sp, P<uint32_t>(c->flagged), P<uint32_t>(c->fbits),
+                                                    P<uint64_t>(c->rec_off), P<uint32_t>(c->rec_cnt),
+                                                    P<gw_sync_record>(c->rec0), c->rec_cap, st, sfirst, slast,
+                                                    max_ents, max_cells, c->sync_halves, ws);
         else
-            launch_sync_write(w, P<uint32_t>(c->flagged), P<uint32_t>(c->fbits), nf, NFM, P<uint64_t>(c->rec_off),
-                              P<uint32_t>(c->rec_cnt), P<gw_sync_record>(c->rec0), c->rec_cap, st, ws,
-                              pairs ? P<uint64_t>(c->gk0) : nullptr, pairs ? P<float4>(c->pay) : nullptr,
-                              sw_halves);
+            write_variant = launch_sync_write(w, P<uint32_t>(c->flagged), P<uint32_t>(c->fbits), nf, NFM,
+                                              P<uint64_t>(c->rec_off), P<uint32_t>(c->rec_cnt),
+                                              P<gw_sync_record>(c->rec0), c->rec_cap, st, ws,
+                                              pairs ? P<uint64_t>(c->gk0) : nullptr,
+                                              pairs ? P<float4>(c->pay) : nullptr, sw_halves);
     };
     write_pass(cs);
     size_t s_write = prof_end(c, 0);
@@ -1580,6 +1587,10 @@ int gw_sync_collect(gw_ctx* c, uint32_t flags, gw_sync_out* out) {
         if ((rc = read_cstats(c))) return rc;
         if (c->hcstats->overflow) return set_err(c, GW_ENOMEM, "sync record buffer overflowed twice");
     }
+    if (c->debug_stats)
+        fprintf(stderr, "gw_sync_collect: flagged %llu rec %llu write=%s gdirect=%d small=%d nb_u=%d G=%u\n",
+                (unsigned long long)NF, (unsigned long long)R, write_variant, gdirect ? 1 : 0, small ? 1 : 0,
+                c->nb_u, G);
     gw_sync_record* recs = P<gw_sync_record>(c->rec0);
     bool gates_done = false;
     if (gdirect) {                                       // the partitions' first records came with the sync

@@ -226,6 +226,17 @@ struct gw_ctx {
     uint32_t dirty_span = 0;
     uint32_t half_rows = 16;             // GW_HALF_ROWS: TickBufs.half_rows (tests of the fallback paths)
     uint32_t gate_lane_max = 255;        // GW_GATE_LANE_MAX: TickBufs.gate_lane_max (tests of the fallback)
+    bool small_on = true;                // GW_SMALL: small-space mode (a block per space, its grid in LDS) for the
+                                         // tick and the collect alike; 0: the general multi-space path
+    bool mover_halves = true;            // GW_MOVER_HALVES: TickBufs.small_halves (0: k_mover_small<2,false>)
+    bool sync_halves = true;             // GW_SYNC_HALVES: k_sync_write_small2 (0: k_sync_write_small<GW_NB_U>)
+    bool gate_counts_on = true;          // GW_GATE_COUNTS: TickBufs.gate_counts (0: the multi-gate collect's count
+                                         // pass walks every window)
+    bool gate_direct_on = true;          // GW_GATE_DIRECT: records straight into their gates' partitions (0: the
+                                         // stable sort by gate)
+    bool debug_stats = false;            // GW_DEBUG_STATS: one stderr line per tick and per collect (the kernel
+                                         // variants launched and their counters)
+    const char* diff_variant = "none";   // tick_diff's kernel of the pending tick's last attempt (debug_stats)
     int32_t bk_flat = -1;                // GW_BK_FLAT, GW_POST_SPLIT, GW_PLACE_SPLIT: TickBufs' launch-merge knobs
     uint32_t post_split = 0, place_split = 0;
     bool dirty_split = false;            // GW_DIRTY_SPLIT=1: the dirty cells' merges in a launch of their own

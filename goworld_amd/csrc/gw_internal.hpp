@@ -346,7 +346,7 @@ void tick_grid(const TickBufs& b, ScanCtx& sc, hipStream_t s, bool dirty = true)
 // b.w: the new grid; pre: the buffers before the flip, whose dirty cells it
 // merges in the bounds' launch (tick_grid ran with dirty = false)
 void tick_movers(const TickBufs& b, ScanCtx& sc, hipStream_t s, const TickBufs* pre = nullptr);
-void tick_diff(const TickBufs& b, hipStream_t s);                  // own + mirror events per mover
+const char* tick_diff(const TickBufs& b, hipStream_t s);           // own + mirror events per mover; the kernel launched
 void tick_events(const TickBufs& b, ScanCtx& sc, hipStream_t s);   // canonical event arrays
 // after the host read the counts (given by value); zeroes the tick's DevStats
 // the per-tick reset (next tick's bucket bounds, zeroed statistics): one block
@@ -366,11 +366,12 @@ void publish_words(const PubSeg* segs, int n, hipStream_t s);
 
 void launch_set_clients(const World& w, const uint32_t* slots, const uint16_t* gates, uint32_t n, bool grid_ok,
                         hipStream_t s);
-// sync collect
-void launch_sync_write_small(const World& w, uint32_t n_spaces, const uint32_t* flagged, const uint32_t* fbits,
-                             const uint64_t* rec_off, const uint32_t* cnt, gw_sync_record* rec, uint64_t rec_cap,
-                             DevStats* st, const uint32_t* sfirst, const uint32_t* slast, uint32_t max_ents,
-                             uint32_t max_cells, hipStream_t s);
+// sync collect (the write launchers return the name of the kernel they
+// launched, "none" when there was nothing to do: GW_DEBUG_STATS)
+const char* launch_sync_write_small(const World& w, uint32_t n_spaces, const uint32_t* flagged, const uint32_t* fbits,
+                                    const uint64_t* rec_off, const uint32_t* cnt, gw_sync_record* rec,
+                                    uint64_t rec_cap, DevStats* st, const uint32_t* sfirst, const uint32_t* slast,
+                                    uint32_t max_ents, uint32_t max_cells, bool halves, hipStream_t s);
 // small-space mode: every space's grid (entries + row starts) in this many LDS bytes at most
 constexpr size_t SMALL_LDS_MAX = 48 * 1024;
 // also zeroes *ovf, the write passes' overflow flag (the collect's only
@@ -386,13 +387,13 @@ void launch_sync_count(const World& w, const uint32_t* flagged, const uint32_t* 
 // its gate's position (sync.hip)
 void launch_sync_gates(const World& w, const uint32_t* flagged, const uint32_t* fbits, const uint64_t* nf_dev,
                        uint32_t nf_max, uint32_t G, uint32_t* cnt, hipStream_t s);
-void launch_sync_write_gates(const World& w, const uint32_t* flagged, const uint32_t* fbits, const uint64_t* nf_dev,
-                             uint32_t nf_max, uint32_t G, const uint64_t* off, gw_sync_record* rec, uint64_t rec_cap,
-                             DevStats* st, hipStream_t s);
-void launch_sync_write(const World& w, const uint32_t* flagged, const uint32_t* fbits, const uint64_t* nf_dev,
-                       uint32_t nf_max, const uint64_t* rec_off, const uint32_t* cnt, gw_sync_record* rec,
-                       uint64_t rec_cap, DevStats* st, hipStream_t s,
-                       uint64_t* pairs = nullptr, float4* pay = nullptr, bool halves = false);
+const char* launch_sync_write_gates(const World& w, const uint32_t* flagged, const uint32_t* fbits,
+                                    const uint64_t* nf_dev, uint32_t nf_max, uint32_t G, const uint64_t* off,
+                                    gw_sync_record* rec, uint64_t rec_cap, DevStats* st, hipStream_t s);
+const char* launch_sync_write(const World& w, const uint32_t* flagged, const uint32_t* fbits, const uint64_t* nf_dev,
+                              uint32_t nf_max, const uint64_t* rec_off, const uint32_t* cnt, gw_sync_record* rec,
+                              uint64_t rec_cap, DevStats* st, hipStream_t s,
+                              uint64_t* pairs = nullptr, float4* pay = nullptr, bool halves = false);
 // the records and the client segment table in one pass (k_records_seg)
 void launch_records_seg(const World& w, const uint64_t* pairs, const uint32_t* idx, const uint32_t* flagged, const float4* pay, uint64_t n, gw_sync_record* out,
                         uint32_t* client_slot, uint64_t* client_off, uint32_t* n_clients, ScanCtx& sc,

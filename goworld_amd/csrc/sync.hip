@@ -830,51 +830,62 @@ __global__ void __launch_bounds__(NT) k_sync_write_small2(World w, const uint32_
     }
 }
 
-void launch_sync_write_small(const World& w, uint32_t n_spaces, const uint32_t* flagged, const uint32_t* fbits,
-                             const uint64_t* rec_off, const uint32_t* cnt, gw_sync_record* rec, uint64_t rec_cap,
-                             DevStats* st, const uint32_t* sfirst, const uint32_t* slast, uint32_t max_ents,
-                             uint32_t max_cells, hipStream_t s) {
-    if (!n_spaces) return;
+// The write launchers return the name of the kernel they launched ("none":
+// nothing to do), printed by gw_sync_collect under GW_DEBUG_STATS.
+const char* launch_sync_write_small(const World& w, uint32_t n_spaces, const uint32_t* flagged, const uint32_t* fbits,
+                                    const uint64_t* rec_off, const uint32_t* cnt, gw_sync_record* rec,
+                                    uint64_t rec_cap, DevStats* st, const uint32_t* sfirst, const uint32_t* slast,
+                                    uint32_t max_ents, uint32_t max_cells, bool halves, hipStream_t s) {
+    if (!n_spaces) return "none";
     const size_t lds = (size_t)max_ents * sizeof(GEnt) + ((size_t)max_cells + 1) * 4;
-    static const bool halves = !getenv("GW_SYNC_HALVES") || atoi(getenv("GW_SYNC_HALVES")) != 0;
     if (halves) {
         hipLaunchKernelGGL(k_sync_write_small2, dim3(n_spaces), dim3(NT), lds, s, w, flagged, fbits, rec_off, cnt,
                            rec, rec_cap, st, sfirst, slast, max_ents);
-        return;
+        return "k_sync_write_small2";
     }
-    if (w.nb_u >= 8)
+    if (w.nb_u >= 8) {
         hipLaunchKernelGGL(k_sync_write_small<8>, dim3(n_spaces), dim3(NT), lds, s, w, flagged, fbits, rec_off, cnt,
                            rec, rec_cap, st, sfirst, slast, max_ents);
-    else if (w.nb_u <= 2)
+        return "k_sync_write_small<8>";
+    }
+    if (w.nb_u <= 2) {
         hipLaunchKernelGGL(k_sync_write_small<2>, dim3(n_spaces), dim3(NT), lds, s, w, flagged, fbits, rec_off, cnt,
                            rec, rec_cap, st, sfirst, slast, max_ents);
-    else
-        hipLaunchKernelGGL(k_sync_write_small<4>, dim3(n_spaces), dim3(NT), lds, s, w, flagged, fbits, rec_off, cnt,
-                           rec, rec_cap, st, sfirst, slast, max_ents);
+        return "k_sync_write_small<2>";
+    }
+    hipLaunchKernelGGL(k_sync_write_small<4>, dim3(n_spaces), dim3(NT), lds, s, w, flagged, fbits, rec_off, cnt,
+                       rec, rec_cap, st, sfirst, slast, max_ents);
+    return "k_sync_write_small<4>";
 }
 
-void launch_sync_write(const World& w, const uint32_t* flagged, const uint32_t* fbits, const uint64_t* nf_dev,
-                       uint32_t nf_max, const uint64_t* rec_off, const uint32_t* cnt, gw_sync_record* rec,
-                       uint64_t rec_cap, DevStats* st, hipStream_t s, uint64_t* pr, float4* pay, bool halves) {
-    if (!nf_max) return;
+const char* launch_sync_write(const World& w, const uint32_t* flagged, const uint32_t* fbits, const uint64_t* nf_dev,
+                              uint32_t nf_max, const uint64_t* rec_off, const uint32_t* cnt, gw_sync_record* rec,
+                              uint64_t rec_cap, DevStats* st, hipStream_t s, uint64_t* pr, float4* pay, bool halves) {
+    if (!nf_max) return "none";
     const dim3 g(std::min(nblk(nf_max, NWAVE), SYNC_MAX_BLOCKS));
     if (halves && !pr) {
         hipLaunchKernelGGL(k_sync_write_h<4>, dim3(std::min(nblk(nf_max, 2 * NWAVE), SYNC_MAX_BLOCKS)), dim3(NT), 0, s,
                            w, flagged, fbits, nf_dev, nf_max, rec_off, cnt, rec, rec_cap, st);
-        return;
+        return "k_sync_write_h<4>";
     }
-    if (pr)
+    if (pr) {
         hipLaunchKernelGGL((k_sync_write<4, true>), g, dim3(NT), 0, s, w, flagged, fbits, nf_dev, nf_max, rec_off, cnt,
                            rec, rec_cap, st, pr, pay);
-    else if (w.nb_u >= 8)
+        return "k_sync_write<4,true>";
+    }
+    if (w.nb_u >= 8) {
         hipLaunchKernelGGL(k_sync_write<8>, g, dim3(NT), 0, s, w, flagged, fbits, nf_dev, nf_max, rec_off, cnt, rec,
                            rec_cap, st, pr, pay);
-    else if (w.nb_u <= 2)
+        return "k_sync_write<8>";
+    }
+    if (w.nb_u <= 2) {
         hipLaunchKernelGGL(k_sync_write<2>, g, dim3(NT), 0, s, w, flagged, fbits, nf_dev, nf_max, rec_off, cnt, rec,
                            rec_cap, st, pr, pay);
-    else
-        hipLaunchKernelGGL(k_sync_write<4>, g, dim3(NT), 0, s, w, flagged, fbits, nf_dev, nf_max, rec_off, cnt, rec,
-                           rec_cap, st, pr, pay);
+        return "k_sync_write<2>";
+    }
+    hipLaunchKernelGGL(k_sync_write<4>, g, dim3(NT), 0, s, w, flagged, fbits, nf_dev, nf_max, rec_off, cnt, rec,
+                       rec_cap, st, pr, pay);
+    return "k_sync_write<4>";
 }
 
 // ---------------------------------------------------------------------------
@@ -1027,13 +1038,15 @@ void launch_sync_gates(const World& w, const uint32_t* flagged, const uint32_t* 
     const dim3 g(std::min(nblk(nf_max, NWAVE * CG_EPW), SYNC_MAX_BLOCKS));   // CG_EPW entries per wave
     hipLaunchKernelGGL(k_sync_count_g<4>, g, dim3(NT), 0, s, w, flagged, fbits, nf_dev, nf_max, G, cnt);
 }
-void launch_sync_write_gates(const World& w, const uint32_t* flagged, const uint32_t* fbits, const uint64_t* nf_dev,
-                             uint32_t nf_max, uint32_t G, const uint64_t* off, gw_sync_record* rec, uint64_t rec_cap,
-                             DevStats* st, hipStream_t s) {
-    if (!nf_max) return;
+const char* launch_sync_write_gates(const World& w, const uint32_t* flagged, const uint32_t* fbits,
+                                    const uint64_t* nf_dev, uint32_t nf_max, uint32_t G, const uint64_t* off,
+                                    gw_sync_record* rec, uint64_t rec_cap,
+                                    DevStats* st, hipStream_t s) {
+    if (!nf_max) return "none";
     const dim3 g(std::min(nblk(nf_max, NWAVE), SYNC_MAX_BLOCKS));
     hipLaunchKernelGGL(k_sync_write_g<4>, g, dim3(NT), 0, s, w, flagged, fbits, nf_dev, nf_max, G, off, rec, rec_cap,
                        st);
+    return "k_sync_write_g<4>";
 }
 
 // 24-B records from sorted (watcher, entity) pairs (through idx, the gate

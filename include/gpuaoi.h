@@ -179,7 +179,12 @@ const char* gw_last_error(const gw_ctx* ctx);
 
 /* Space.EnableAOI(d): d > 0.  bounds = {minx, minz, maxx, maxz} sizes the
  * uniform grid (NULL = Space.GetSpaceRange default, Space.go:52-54); entities
- * outside the bounds are still exact (clamped cells), only slower. */
+ * outside the bounds are still exact (clamped cells), only slower.
+ * A space's grid has at most 4096 x 4096 cells (cells of side aoi_dist / 2,
+ * or larger where the bounds need it), and the grids of all spaces of a
+ * context share one cell range of fewer than 2^25 cells (destroyed spaces'
+ * ranges are reused): a create that would pass it fails with GW_ERANGE ("too
+ * many grid cells") and changes nothing. */
 int  gw_space_create(gw_ctx* ctx, float aoi_dist, uint32_t capacity,
                      const float* bounds, uint32_t* space_id, uint32_t* slot_base);
 /* Space.OnDestroy -> SpaceManager.delSpace (Space.go:143-151,

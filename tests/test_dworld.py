@@ -72,12 +72,14 @@ def _sort_rec(r):
 TELEPORT = dict(TRACE, teleports=3)
 
 
-def _check(world, results, trace=TRACE):
+def _check(world, results, trace=TRACE, gates=None):
+    """gates: the gate id of every slot when the ranks ran with another layout
+    than the trace's own (the oracle then gets the same)."""
     tr = T.strip_world_trace(trace["seed"], trace["n"], world, trace["strip_w"], trace["height"],
                              trace["d"], trace["ticks"], trace["max_step"], teleports=trace.get("teleports", 0),
                              groups=trace.get("groups", 0))
     o = pyorc.OracleSpace(tr.n, tr.d, pyorc.SEQRULE)
-    o.set_clients(tr.gates)
+    o.set_clients(tr.gates if gates is None else gates)
     n_ev = n_rec = 0
     for t in range(len(tr.ticks)):
         assert o.tick(tr.global_ops(t)) == 0

@@ -205,3 +205,33 @@ def test_destroy_refuses_a_non_empty_space_after_device_submits():
         g.dev_free(dev)
     finally:
         g.close()
+
+
+def test_context_cell_limit():
+    """The grids of all spaces of a context share one cell index space of fewer
+    than 2^25 cells (gpuaoi.h, gw_space_create).  A space of 4096 x 4096 cells
+    takes half of it; a second one is refused with GW_ERANGE, and the refusal
+    leaves the context's ranges untouched: a small space created afterwards
+    runs the adversarial trace bit-exactly (XZList restatement), with the
+    large space's 2^24 cells in every grid pass.  The large space is then
+    destroyed."""
+    from test_gpu_parity import Harness
+    big = (0.0, 0.0, 4096 * 50.0, 4096 * 50.0)              # d = 100: cells of 50
+    with gpuaoi.GpuAOI(0) as g:
+        sid, base = g.create_space(100.0, 8, big)
+        info = g.context_info()
+        with pytest.raises(gpuaoi.GwError, match="too many grid cells") as ei:
+            g.create_space(100.0, 8, big)
+        assert ei.value.code == -5                          # GW_ERANGE
+        assert g.context_info() == info                     # totals and free lists as before
+        tr = T.adversarial_trace(13, n=300, ticks=12, leave_masks=True)
+        h = Harness(g, [tr], mode=pyorc.XZLIST)
+        assert h.bases[0] == base + 8                       # the refused space took no slots
+        h.check_collect()
+        for t in range(len(tr.ticks)):
+            h.step(t)
+            h.check_collect()
+        h.check_lists(sample=range(0, tr.capacity, 5))
+        g.destroy_space(sid)
+        after = g.context_info()
+        assert (after["live_spaces"], after["live_cells"]) == (1, 20 * 20)

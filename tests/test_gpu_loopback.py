@@ -84,19 +84,45 @@ class LoopbackRuns:
             th.stop()
 
 
-@pytest.mark.parametrize("world,trace", [(3, "teleports"), (4, "teleports"), (2, "groups"), (3, "groups"),
-                                         (4, "groups")])
-def test_loopback_world_teleports_vs_oracle(world, trace):
+def _gate_layout(name, n):
+    """Gate ids per slot: None keeps the trace's own 0..3 (G = 4: two gate words
+    per lane in k_mover_c), "ones" one gate (G = 2: no split by gate), "wide"
+    ids 0..12 (G = 13: four gate words per lane)."""
+    i = np.arange(n)
+    if name == "ones":
+        return np.ones(n, np.uint16)
+    if name == "wide":
+        return np.where(i % 5 == 4, 0, 1 + i % 12).astype(np.uint16)
+    return None
+
+
+DIFF_OF_LAYOUT = {None: "k_mover_c<2,1,2>", "ones": "k_mover_c<2,1,0>", "wide": "k_mover_c<2,1,4>"}
+
+
+# (the first five ids are the cases as they were before the gate layouts)
+@pytest.mark.parametrize("world,trace,layout", [
+    pytest.param(3, "teleports", None, id="3-teleports"), pytest.param(4, "teleports", None, id="4-teleports"),
+    pytest.param(2, "groups", None, id="2-groups"), pytest.param(3, "groups", None, id="3-groups"),
+    pytest.param(4, "groups", None, id="4-groups"),
+    pytest.param(2, "groups", "ones", id="2-groups-ones"), pytest.param(3, "groups", "ones", id="3-groups-ones"),
+    pytest.param(2, "groups", "wide", id="2-groups-wide"), pytest.param(3, "groups", "wide", id="3-groups-wide")])
+def test_loopback_world_teleports_vs_oracle(world, trace, layout, monkeypatch, capfd):
     """Strip trace with churn, Leave + re-Enter inside a tick, Sync ops and long
     moves per tick across two or more strips (groups: related entities jumping
     together, apart or next to each other, whose pairs come from the long-mover
     lists), through gw_world_step on every rank thread; the union of the
-    ranks' owned events and records equals one global oracle space."""
+    ranks' owned events and records equals one global oracle space.  The gate
+    layouts select k_mover_c's long-mover instantiations by gate words (0, 2,
+    4): every tick line of every rank (GW_DEBUG_STATS) must name the expected
+    one."""
+    monkeypatch.setenv("GW_DEBUG_STATS", "1")               # gw_init reads it
     TR = TELEPORT if trace == "teleports" else GROUPS
     tr = T.strip_world_trace(TR["seed"], TR["n"], world, TR["strip_w"], TR["height"], TR["d"], TR["ticks"],
                              TR["max_step"], teleports=TR["teleports"], groups=TR.get("groups", 0))
     geom = dworld.Strips(0.0, tr.strip_w, world, tr.d, tr.max_step)
-    lw = dworld.LoopbackWorld(geom, tr.n, tr.bounds, gates=tr.gates)
+    gates = _gate_layout(layout, tr.n)
+    capfd.readouterr()
+    lw = dworld.LoopbackWorld(geom, tr.n, tr.bounds, gates=tr.gates if gates is None else gates)
     try:
         ptrs = [[lw.upload(r, tr.rank_ops(t, r)) for r in range(world)] for t in range(len(tr.ticks))]
         collect_every = 3
@@ -117,7 +143,11 @@ def test_loopback_world_teleports_vs_oracle(world, trace):
         lw.close()
     far = sum(x.pop("far") for x in results)
     assert world < 3 or far > 0                            # the far round moved rows
-    _check(world, results, trace=TR)
+    _check(world, results, trace=TR, gates=gates)
+    ticks = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("gw_tick:")]
+    for r in range(world):                                 # per rank thread: the long-mover kernel of this layout
+        mine = [ln.split(" diff=")[1].split()[0] for ln in ticks if ln.endswith(f" rank={r}")]
+        assert mine and set(mine) == {DIFF_OF_LAYOUT[layout]}, (r, set(mine))
 
 
 def test_loopback_world_1m_8_strips_equals_single_context():

@@ -66,8 +66,9 @@ class Harness:
     Positions are tracked from the ops to predict the record stream's exact
     order (the walk's grid order)."""
 
-    def __init__(self, g, trs, mode=pyorc.SEQRULE):
+    def __init__(self, g, trs, mode=pyorc.SEQRULE, cells_per_d=2):
         self.g, self.trs = g, trs
+        self.cells_per_d = cells_per_d              # the context's GW_CELLS_PER_D (the record order's grid)
         self.orcs, self.bases = [], []
         cap_total = 0
         self.x, self.z = [], []
@@ -98,7 +99,7 @@ class Harness:
         exp, keys = [], []
         for i, (o, b, tr) in enumerate(zip(self.orcs, self.bases, self.trs)):
             e = o.collect()
-            cell = grid_cells(tr, self.x[i][e["watcher"]], self.z[i][e["watcher"]])
+            cell = grid_cells(tr, self.x[i][e["watcher"]], self.z[i][e["watcher"]], self.cells_per_d)
             own = e["watcher"] == e["entity"]
             e["watcher"] += b
             e["entity"] += b
