@@ -52,12 +52,14 @@ type SyncInfoSource interface {
 	AOISyncInfo() proto.EntitySyncInfo
 }
 
-// entInfo: what the wire records need of an entity (ids and client) and its
-// SetClientSyncing flag; applied to whichever slot the entity holds.
+// entInfo: what the wire records need of an entity (ids and client), its
+// SetClientSyncing flag and its query tag; applied to whichever slot the
+// entity holds.
 type entInfo struct {
 	eid, cid [16]byte
 	gate     uint16
 	syncing  bool
+	tag      uint32 // query tag (SetTag, query.go)
 }
 
 type parkRef struct {
@@ -527,9 +529,9 @@ func (c *Context) ClearIDs(a *aoi.AOI) {
 	delete(c.idDirty, a)
 }
 
-// applyIDs writes the registered ids, client and syncing flag of every entity
-// that got a slot or changed them since the last call, at its slot, in one
-// batch per table.
+// applyIDs writes the registered ids, client, syncing flag and query tag of
+// every entity that got a slot or changed them since the last call, at its
+// slot, in one batch per table.
 func (c *Context) applyIDs() {
 	if len(c.idDirty) == 0 {
 		return
@@ -538,6 +540,7 @@ func (c *Context) applyIDs() {
 	var eids, cids []byte
 	var gates []C.uint16_t
 	var on []C.uint8_t
+	var tags []C.uint32_t
 	for a := range c.idDirty {
 		m := c.cur[a]
 		if m == nil {
@@ -555,6 +558,7 @@ func (c *Context) applyIDs() {
 		eids = append(eids, e.eid[:]...)
 		cids = append(cids, e.cid[:]...)
 		gates = append(gates, C.uint16_t(e.gate))
+		tags = append(tags, C.uint32_t(e.tag))
 		var b C.uint8_t
 		if e.syncing {
 			b = 1
@@ -572,6 +576,7 @@ func (c *Context) applyIDs() {
 	c.check(C.gw_set_client_ids(c.ctx, &slots[0], unsafe.Pointer(&cids[0]), n))
 	c.check(C.gw_set_clients(c.ctx, &slots[0], &gates[0], n))
 	c.check(C.gw_set_client_syncing(c.ctx, &slots[0], &on[0], n))
+	c.check(C.gw_set_tags(c.ctx, &slots[0], &tags[0], n))
 }
 
 // ClientSync is HandleSyncPositionYawFromClient (GameService.go:395-407): the

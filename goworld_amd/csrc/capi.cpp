@@ -238,6 +238,7 @@ int grow_slots(gw_ctx* c, uint32_t new_total) {
     if ((rc = grow_preserve(c, c->gmi, 0, (size_t)nc))) return rc;
     if ((rc = grow_preserve(c, c->eid_dev, oc, nc))) return rc;
     if ((rc = grow_preserve(c, c->cid_dev, oc, nc))) return rc;
+    if ((rc = grow_preserve(c, c->tags, oc, nc))) return rc;
     if ((rc = grow_preserve(c, c->ol, oc, nc))) return rc;     // new records: zero (session 0 is never used)
     if ((rc = grow_preserve(c, c->gnb[0], 0, nc))) return rc;    // rebuilt (grid_dirty)
     if ((rc = grow_preserve(c, c->gnb[1], 0, nc))) return rc;
@@ -249,6 +250,7 @@ int grow_slots(gw_ctx* c, uint32_t new_total) {
     HIPCHK(hipMemsetAsync(c->movbit, 0, ((size_t)nc / 32 + 1) * 4, c->st));
     HIPCHK(hipMemsetAsync(c->eid_dev + oc, 0, n * 16, c->st));
     HIPCHK(hipMemsetAsync(c->cid_dev + oc, 0, n * 16, c->st));
+    HIPCHK(hipMemsetAsync(c->tags + oc, 0, n * 4, c->st));
     HIPCHK(hipMemsetAsync(c->ol + oc, 0, n * sizeof(OpLast), c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     c->slot_cap = nc;
@@ -265,7 +267,7 @@ World world(gw_ctx* c);
 // slots [base, base + n): absent, in space `sid`, every other per-slot array
 // cleared (a reused range, or fresh zeros from grow_slots)
 int init_space_slots(gw_ctx* c, uint32_t base, uint32_t n, uint32_t sid) {
-    launch_slots_clear(world(c), c->ol, c->eid_dev, c->cid_dev, base, n, sid, c->st);
+    launch_slots_clear(world(c), c->ol, c->eid_dev, c->cid_dev, c->tags, base, n, sid, c->st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;
@@ -601,7 +603,9 @@ void gw_shutdown(gw_ctx* c) {
                       &c->fbits, &c->flagged, &c->rec_cnt, &c->rec_off, &c->rec0, &c->rec1,
                       &c->gate_hist, &c->gk0, &c->gv0, &c->gk1, &c->gv1, &c->qbuf, &c->cl_slot, &c->cl_off,
                       &c->m_create.a, &c->m_create.b, &c->m_destroy.a, &c->m_destroy.b, &c->m_fanout.a,
-                      &c->m_fanout.b, &c->m_flag, &c->m_at, &c->m_items, &c->m_cnt, &c->m_off};
+                      &c->m_fanout.b, &c->m_flag, &c->m_at, &c->m_items, &c->m_cnt, &c->m_off,
+                      &c->q_slots, &c->q_cnt, &c->q_lcnt, &c->q_off, &c->q_loff, &c->q_nbr, &c->q_near, &c->q_nslots,
+                      &c->q_rel, &c->q_stat};
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     DevBuf* wb[] = {&c->wd.stamps, &c->wd.send[0], &c->wd.send[1], &c->wd.recv[0], &c->wd.recv[1], &c->wd.cnt,
                     &c->wire_d, &c->wire_tab, &c->id_up, &c->wd.ext, &c->wd.far_rows, &c->wd.far_dest,
@@ -613,10 +617,11 @@ void gw_shutdown(gw_ctx* c) {
     if (c->wd.staged) (void)hipEventDestroy(c->wd.staged);
     if (c->eid_dev) (void)hipFree(c->eid_dev);
     if (c->cid_dev) (void)hipFree(c->cid_dev);
+    if (c->tags) (void)hipFree(c->tags);
     for (DevBuf* b : wb) if (b->p) (void)hipFree(b->p);
     xp_release(c);
     DevBuf* hb[] = {&c->h_enter, &c->h_leave, &c->h_rec, &c->h_cl_slot, &c->h_cl_off, &c->h_items, &c->m_create.h,
-                    &c->m_destroy.h, &c->m_fanout.h};
+                    &c->m_destroy.h, &c->m_fanout.h, &c->h_qnbr, &c->h_qoff, &c->h_qnear, &c->h_qrel, &c->h_qstat};
     for (DevBuf* b : hb) if (b->p) (void)hipHostFree(b->p);
     void* ps[] = {c->halo, c->sc.ticket, c->sc2.ticket, c->movbit, c->gmi, c->rec, c->flags, c->gate, c->nbc, c->nbg, c->ol,
                   c->gnb[0], c->gnb[1], c->sp_dev, c->stats, c->scal32, c->gsb[0],
@@ -807,7 +812,7 @@ int gw_space_destroy(gw_ctx* c, uint32_t sid_h) {
     int rc;
     if ((rc = count_present(c, s.base, s.cap, &np))) return rc;
     if (np) return set_err(c, GW_ESTATE, "space %u not empty (%llu entities)", sid, (unsigned long long)np);
-    launch_slots_clear(world(c), c->ol, c->eid_dev, c->cid_dev, s.base, s.cap, sid, c->st);
+    launch_slots_clear(world(c), c->ol, c->eid_dev, c->cid_dev, c->tags, s.base, s.cap, sid, c->st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->st));
     move_host_slots(c, s.base, s.cap, -1);
@@ -869,9 +874,9 @@ int gw_space_grow(gw_ctx* c, uint32_t sid_h, uint32_t new_capacity, uint32_t* ne
     (void)take_range(c->free_slots, c->total_slots, new_capacity, true, &nt);
     c->total_slots = nt;
     const World w = world(c);
-    launch_slots_clear(w, c->ol, c->eid_dev, c->cid_dev, nb + s.cap, delta, sid, c->st);
-    launch_slots_move(w, c->ol, c->eid_dev, c->cid_dev, s.base, nb, s.cap, c->st);
-    launch_slots_clear(w, c->ol, c->eid_dev, c->cid_dev, s.base, s.cap, sid, c->st);
+    launch_slots_clear(w, c->ol, c->eid_dev, c->cid_dev, c->tags, nb + s.cap, delta, sid, c->st);
+    launch_slots_move(w, c->ol, c->eid_dev, c->cid_dev, c->tags, s.base, nb, s.cap, c->st);
+    launch_slots_clear(w, c->ol, c->eid_dev, c->cid_dev, c->tags, s.base, s.cap, sid, c->st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->st));
     const uint32_t ob = s.base, oc = s.cap;
@@ -1988,6 +1993,207 @@ int gw_total_neighbors(gw_ctx* c, uint64_t* out) {
     HIPCHK(hipMemcpyAsync(&t, c->scal32, 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     *out = t;
+    return 0;
+}
+
+// ---- batched InterestedIn queries (query.hip) --------------------------------
+// Every query sees the state of the last flush: settle, then the grid.
+
+// host slots checked while they are staged in pinned memory (as gw_fanout's)
+static int stage_slots(gw_ctx* c, const char* what, const uint32_t* const* srcs, int nsrc, uint32_t n, DevBuf& dev) {
+    int rc;
+    if ((rc = ensure_host(c, c->h_items, (size_t)n * 4 * nsrc)) || (rc = ensure(c, dev, (size_t)n * 4 * nsrc)))
+        return rc;
+    uint32_t* hi = (uint32_t*)c->h_items.p;
+    const uint32_t C = c->total_slots;
+    for (int j = 0; j < nsrc; ++j) {
+        uint32_t bad = 0;
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t s = srcs[j][k];
+            bad |= s >= C;
+            hi[(size_t)j * n + k] = s;
+        }
+        if (bad)
+            for (uint32_t k = 0; k < n; ++k)
+                if (srcs[j][k] >= C) return set_err(c, GW_ERANGE, "%s: slot %u out of range", what, srcs[j][k]);
+    }
+    HIPCHK(hipMemcpyAsync(dev.p, hi, (size_t)n * 4 * nsrc, hipMemcpyHostToDevice, c->st));
+    return 0;
+}
+
+// the call's statistics (QS_SHARDS x {candidates, matches}) summed on the host
+static void query_stats(const gw_ctx* c, uint64_t* cand, uint64_t* match) {
+    const unsigned long long* h = (const unsigned long long*)c->h_qstat.p;
+    *cand = *match = 0;
+    for (uint32_t i = 0; i < QS_SHARDS; ++i) {
+        *cand += h[2 * i];
+        *match += h[2 * i + 1];
+    }
+}
+constexpr size_t QSTAT_BYTES = (size_t)QS_SHARDS * 2 * 8;
+
+int gw_set_tags(gw_ctx* c, const uint32_t* slots, const uint32_t* tags, uint32_t n) {
+    if (!c || (n && (!slots || !tags))) return GW_EINVAL;
+    if (!n) return 0;
+    (void)hipSetDevice(c->dev);
+    int rc;
+    // all or nothing: every slot is checked before anything is staged
+    for (uint32_t k = 0; k < n; ++k)
+        if (slots[k] >= c->total_slots) return set_err(c, GW_ERANGE, "set_tags: slot %u out of range", slots[k]);
+    if ((rc = ensure_host(c, c->h_items, (size_t)n * 8)) || (rc = ensure(c, c->q_slots, (size_t)n * 8))) return rc;
+    uint32_t* hi = (uint32_t*)c->h_items.p;
+    memcpy(hi, slots, (size_t)n * 4);
+    memcpy(hi + n, tags, (size_t)n * 4);
+    HIPCHK(hipMemcpyAsync(c->q_slots.p, hi, (size_t)n * 8, hipMemcpyHostToDevice, c->st));
+    launch_set_tags(c->tags, P<uint32_t>(c->q_slots), P<uint32_t>(c->q_slots) + n, n, c->total_slots, c->st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->st));   // the pinned staging buffer is reused by the next call
+    return 0;
+}
+
+int gw_neighbors_batch(gw_ctx* c, const uint32_t* slots, uint32_t n, uint32_t tag_mask, uint32_t tag_value,
+                       uint32_t flags, gw_nbr_out* out) {
+    if (!c || !out || (n && !slots)) return GW_EINVAL;
+    int rc;
+    if ((rc = settle(c))) return rc;
+    (void)hipSetDevice(c->dev);
+    const uint32_t* dslots = slots;
+    if (n && !(flags & GW_QUERY_SLOTS_ON_DEVICE)) {
+        if ((rc = stage_slots(c, "neighbors_batch", &slots, 1, n, c->q_slots))) return rc;
+        dslots = P<uint32_t>(c->q_slots);
+    }
+    memset(out, 0, sizeof *out);
+    if ((rc = ensure(c, c->q_off, ((size_t)n + 1) * 8)) || (rc = ensure(c, c->q_loff, ((size_t)n + 1) * 8)) ||
+        (rc = ensure(c, c->q_cnt, (size_t)n * 4)) || (rc = ensure(c, c->q_lcnt, (size_t)n * 4)) ||
+        (rc = ensure(c, c->q_stat, QSTAT_BYTES)) || (rc = ensure_host(c, c->h_qstat, QSTAT_BYTES)) ||
+        (rc = ensure(c, c->q_nbr, 16)))
+        return rc;
+    HIPCHK(hipEventRecord(c->ev_t0, c->st));
+    uint64_t tot[2] = {0, 0};   // list entries; those of the lists on the general ordering path
+    uint64_t* off = P<uint64_t>(c->q_off);
+    uint64_t* loff = P<uint64_t>(c->q_loff);
+    const uint32_t lmin = (flags & GW_QUERY_GENERAL_ORDER) ? 0u : QL_LDS_MAX;
+    unsigned long long* qs = P<unsigned long long>(c->q_stat);
+    HIPCHK(hipMemsetAsync(qs, 0, QSTAT_BYTES, c->st));
+    if (n) {
+        if ((rc = rebuild_grid(c)) || (rc = ensure_scan(c, n))) return rc;
+        const World w = world(c);
+        launch_query_count(w, dslots, n, c->tags, tag_mask, tag_value, lmin, P<uint32_t>(c->q_cnt),
+                           P<uint32_t>(c->q_lcnt), qs, c->st);
+        scan_u32_u64(P<uint32_t>(c->q_cnt), off, n, nullptr, c->sc, off + n, c->st);      // the total behind the offsets
+        scan_u32_u64(P<uint32_t>(c->q_lcnt), loff, n, nullptr, c->sc, loff + n, c->st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&tot[0], off + n, 8, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipMemcpyAsync(&tot[1], loff + n, 8, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));       // the one host read: sizes the output
+    } else {
+        HIPCHK(hipMemsetAsync(off, 0, 8, c->st));
+    }
+    const uint64_t R = tot[0], L = tot[1];
+    if (R) {
+        if ((rc = ensure(c, c->q_nbr, R * 4))) return rc;
+        RadixTmp rt{};
+        if (L) {
+            if ((rc = ensure(c, c->gk0, L * 8)) || (rc = ensure(c, c->gk1, L * 8)) || (rc = radix_tmp(c, L, rt)))
+                return rc;
+        }
+        const World w = world(c);
+        launch_query_write(w, dslots, n, c->tags, tag_mask, tag_value, lmin, off, loff, P<uint32_t>(c->q_nbr),
+                           P<uint64_t>(c->gk0), qs, c->st);
+        if (L) {
+            // the long lists' (query, slot) pairs: a stable sort by slot, then by
+            // query index, and each lands at its list's offset
+            uint64_t* p = P<uint64_t>(c->gk0);
+            uint64_t* q = P<uint64_t>(c->gk1);
+            if (sort_pairs64(p, q, L, nullptr, 0, ceil_log2(c->total_slots), rt, c->st)) std::swap(p, q);
+            launch_pairs_swap(p, L, c->st);
+            if (sort_pairs64(p, q, L, nullptr, 0, ceil_log2(n), rt, c->st)) std::swap(p, q);
+            launch_pairs_place(p, L, off, loff, P<uint32_t>(c->q_nbr), c->st);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    out->nbr_dev = P<uint32_t>(c->q_nbr);
+    out->off_dev = off;
+    out->n_nbr = R;
+    out->n_query = n;
+    if (flags & GW_QUERY_COPY_TO_HOST) {
+        if ((rc = ensure_host(c, c->h_qoff, ((size_t)n + 1) * 8)) || (rc = ensure_host(c, c->h_qnbr, R * 4))) return rc;
+        HIPCHK(hipMemcpyAsync(c->h_qoff.p, off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->st));
+        if (R) HIPCHK(hipMemcpyAsync(c->h_qnbr.p, c->q_nbr.p, R * 4, hipMemcpyDeviceToHost, c->st));
+        out->off = (const uint64_t*)c->h_qoff.p;
+        out->nbr = (const uint32_t*)c->h_qnbr.p;
+    }
+    HIPCHK(hipMemcpyAsync(c->h_qstat.p, qs, QSTAT_BYTES, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipEventRecord(c->ev_t1, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    uint64_t cand, match;
+    query_stats(c, &cand, &match);
+    out->bytes_alg = cand * 16 + R * 4 + ((uint64_t)n + 1) * 8 + (uint64_t)n * 4;
+    float ms_ = 0;
+    (void)hipEventElapsedTime(&ms_, c->ev_t0, c->ev_t1);
+    out->device_us = ms_ * 1000.0;
+    return 0;
+}
+
+int gw_nearest(gw_ctx* c, const uint32_t* slots, uint32_t n, uint32_t tag_mask, uint32_t tag_value, uint32_t flags,
+               gw_near_out* out) {
+    if (!c || !out || (n && !slots)) return GW_EINVAL;
+    int rc;
+    if ((rc = settle(c))) return rc;
+    (void)hipSetDevice(c->dev);
+    const uint32_t* dslots = slots;
+    if (n && !(flags & GW_QUERY_SLOTS_ON_DEVICE)) {
+        if ((rc = stage_slots(c, "nearest", &slots, 1, n, c->q_nslots))) return rc;
+        dslots = P<uint32_t>(c->q_nslots);
+    }
+    memset(out, 0, sizeof *out);
+    if ((rc = ensure(c, c->q_near, (size_t)n * sizeof(gw_nearest_rec))) || (rc = ensure(c, c->q_stat, QSTAT_BYTES)) ||
+        (rc = ensure_host(c, c->h_qstat, QSTAT_BYTES)))
+        return rc;
+    if ((flags & GW_QUERY_COPY_TO_HOST) && (rc = ensure_host(c, c->h_qnear, (size_t)n * sizeof(gw_nearest_rec))))
+        return rc;
+    if (n && (rc = rebuild_grid(c))) return rc;
+    unsigned long long* qs = P<unsigned long long>(c->q_stat);
+    // one launch, then the copies: no host sync before the result is on its way
+    HIPCHK(hipEventRecord(c->ev_t0, c->st));
+    HIPCHK(hipMemsetAsync(qs, 0, QSTAT_BYTES, c->st));
+    launch_nearest(world(c), dslots, n, c->tags, tag_mask, tag_value, P<gw_nearest_rec>(c->q_near), qs, c->st);
+    HIPCHK(hipGetLastError());
+    out->rec_dev = P<gw_nearest_rec>(c->q_near);
+    out->n_query = n;
+    if (flags & GW_QUERY_COPY_TO_HOST) {
+        if (n)
+            HIPCHK(hipMemcpyAsync(c->h_qnear.p, c->q_near.p, (size_t)n * sizeof(gw_nearest_rec), hipMemcpyDeviceToHost,
+                                  c->st));
+        out->rec = (const gw_nearest_rec*)c->h_qnear.p;
+    }
+    HIPCHK(hipMemcpyAsync(c->h_qstat.p, qs, QSTAT_BYTES, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipEventRecord(c->ev_t1, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    uint64_t cand, match;
+    query_stats(c, &cand, &match);
+    out->bytes_alg = cand * 16 + match * 64 + (uint64_t)n * (sizeof(gw_nearest_rec) + 4);
+    float ms_ = 0;
+    (void)hipEventElapsedTime(&ms_, c->ev_t0, c->ev_t1);
+    out->device_us = ms_ * 1000.0;
+    return 0;
+}
+
+int gw_related(gw_ctx* c, const uint32_t* a, const uint32_t* b, uint32_t n, uint8_t* out) {
+    if (!c || (n && (!a || !b || !out))) return GW_EINVAL;
+    int rc;
+    if ((rc = settle(c))) return rc;
+    if (!n) return 0;
+    (void)hipSetDevice(c->dev);
+    const uint32_t* srcs[2] = {a, b};
+    if ((rc = stage_slots(c, "related", srcs, 2, n, c->q_slots))) return rc;
+    if ((rc = ensure(c, c->q_rel, n)) || (rc = ensure_host(c, c->h_qrel, n))) return rc;
+    // straight from the two slots' states: no grid
+    launch_related(world(c), P<uint32_t>(c->q_slots), P<uint32_t>(c->q_slots) + n, n, P<uint8_t>(c->q_rel), c->st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_qrel.p, c->q_rel.p, n, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    memcpy(out, c->h_qrel.p, n);
     return 0;
 }
 

@@ -270,6 +270,11 @@ struct gw_ctx {
     } m_create, m_destroy, m_fanout;
     DevBuf m_flag, m_at, m_items, m_cnt, m_off;
     uint32_t* scal32 = nullptr;    // small device scalars
+    // batched queries (gw_set_tags, gw_neighbors_batch, gw_nearest, gw_related)
+    uint32_t* tags = nullptr;      // [slot_cap] the caller's tag of each slot (read by query.hip only)
+    DevBuf q_slots, q_cnt, q_lcnt, q_off, q_loff, q_nbr;   // lists: staged slots, counts, offsets, the CSR
+    DevBuf q_nslots, q_near, q_rel, q_stat;                // nearest: staged slots, records; pairs; call statistics
+    DevBuf h_qnbr, h_qoff, h_qnear, h_qrel, h_qstat;       // pinned host copies
 
     // host mirror for validation of host-submitted ops
     std::vector<uint8_t> present_h;

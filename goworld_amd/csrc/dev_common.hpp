@@ -1,4 +1,4 @@
-// dev_common.hpp — device helpers shared by aoi.hip and sync.hip: cell
+// dev_common.hpp — device helpers shared by aoi.hip, sync.hip and query.hip: cell
 // search, window tests, the stamp-resolved pair relation, wave/block sorts.
 //
 // Window arithmetic follows go-aoi's XZList Mark bounds:
@@ -249,6 +249,59 @@ __device__ __forceinline__ bool resolve(bool ia, bool ib, unsigned long long sa,
     return sa > sb ? ia : ib;
 }
 
+// ---------------------------------------------------------------------------
+// neighbours of a present entity e from the current grid: calls
+// f(rel, w, client) per lane for every candidate (rel: w != e is related to e;
+// client: w's grid-entry bits CLIENT_BIT | gate id < 16, 0 without a client).
+// The window's row ranges are walked flattened, NB_U chunks of 64 in flight.
+// (wave_neighbors_of: e's state a and its space P already loaded)
+template <int NB_U = 4, typename F>
+__device__ __forceinline__ void wave_neighbors_of(const World& w, uint32_t e, const AoiEnt& a, const SpaceP& P, F f) {
+    const float d = P.d;
+    const Win we = win_of(a.x, a.z, d);
+    Rects R;
+    R.n = 1;
+    R.r[0] = search_rect(P, a.x, a.z);
+    Flat fl = flat_build<1>(P, R, w.gn_start, nullptr);
+    unsigned long long se = 0;
+    bool have_se = false;
+    for (uint32_t base = 0; base < fl.total; base += 64u * NB_U) {
+        uint32_t idx[NB_U], kd[NB_U];
+        flat_map_walk<NB_U, 1>(fl, base, idx, kd);
+        GEnt gg[NB_U];
+#pragma unroll
+        for (int u = 0; u < NB_U; ++u) {
+            gg[u].slot = e;
+            if (idx[u] != ~0u) gg[u] = w.gn[idx[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < NB_U; ++u) {
+            if (base + 64u * u >= fl.total) break;            // wave-uniform
+            bool rel = false;
+            const GEnt g = gg[u];
+            if (g.slot != e) {
+                bool ia, near;
+                we.test(g.x, g.z, ia, near);              // B's test of A only in the rounding band
+                rel = ia;
+                if (near) {
+                    const bool ib = in_win(g.x, g.z, d, a.x, a.z);
+                    if (ia != ib) {
+                        if (!have_se) { se = w.rec[e].stamp; have_se = true; }
+                        rel = resolve(ia, ib, se, w.rec[g.slot].stamp);
+                    }
+                }
+            }
+            f(rel, g.slot, g.meta & (CLIENT_BIT | GATE_MASK));
+        }
+    }
+}
+template <int NB_U = 4, typename F>
+__device__ __forceinline__ void wave_neighbors(const World& w, uint32_t e, F f) {
+    const AoiEnt a = w.rec[e].a;
+    if (!(a.meta & PRESENT_BIT)) return;
+    wave_neighbors_of<NB_U>(w, e, a, w.sp[a.meta & SPACE_MASK], f);
+}
+
 __device__ __forceinline__ uint32_t next_pow2(uint32_t v) {
     if (v <= 1) return 1;
     return 1u << (32 - __clz(v - 1));
@@ -354,10 +407,12 @@ __device__ __forceinline__ uint32_t half_sort32(uint32_t v) {
 // partners i ^ (k-1)).  Every exchange moves the smaller key to the lower
 // index, so the virtual +inf padding past n never moves and n need not be a
 // power of two.  `sync` orders the steps (wave barrier or __syncthreads).
+// k0 > 2: the aligned runs of k0 / 2 are ascending already (only the merge
+// levels from k0 up run).
 template <int TPM, typename T, typename KeyF, typename SyncF>
-__device__ __forceinline__ void bitonic_inplace(T* a, uint32_t n, int t, KeyF key, SyncF sync) {
+__device__ __forceinline__ void bitonic_inplace(T* a, uint32_t n, int t, KeyF key, SyncF sync, uint32_t k0 = 2) {
     const uint32_t P2 = next_pow2(n);
-    for (uint32_t k = 2; k <= P2; k <<= 1) {
+    for (uint32_t k = k0; k <= P2; k <<= 1) {
         const uint32_t h = k >> 1;
         const int lh = __builtin_ctz(h);                 // powers of two: shifts, no integer division
         for (uint32_t i = t; i < (P2 >> 1); i += TPM) {

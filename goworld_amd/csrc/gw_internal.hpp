@@ -407,6 +407,31 @@ void launch_gather_records(const gw_sync_record* in, const uint32_t* idx, const 
 // queries
 void launch_neighbors(const World& w, uint32_t slot, uint32_t* out, uint32_t* n_out, uint32_t cap, hipStream_t s);
 void launch_count_all(const World& w, uint64_t n_present, unsigned long long* total, hipStream_t s);
+// batched queries (query.hip).  tags: the slot-indexed tag array (read only
+// there); a related entity w matches when (tags[w] & mask) == value.
+// qs: QS_SHARDS x {candidates walked, matches} of the call, zeroed by the caller.
+constexpr uint32_t QL_WAVE_MAX = 64;      // a list up to this long is ordered in registers
+constexpr uint32_t QL_LDS_MAX = 1024;     // ... up to this long in the wave's LDS buffer; longer: the radix sorts
+constexpr uint32_t QS_SHARDS = 256;
+// lmin: lists longer than this take the general ordering path (QL_LDS_MAX, or 0: every list);
+// cnt[k] = entries of list k, lcnt[k] = the same if it takes the general path, else 0
+void launch_query_count(const World& w, const uint32_t* slots, uint32_t n, const uint32_t* tags, uint32_t mask,
+                        uint32_t value, uint32_t lmin, uint32_t* cnt, uint32_t* lcnt, unsigned long long* qs,
+                        hipStream_t s);
+// off[n + 1], loff[n]: exclusive scans of cnt / lcnt (off[n] = the total); short lists go to nbr in slot
+// order, the others to pairs (query << 32 | slot) at loff[k] in walk order
+void launch_query_write(const World& w, const uint32_t* slots, uint32_t n, const uint32_t* tags, uint32_t mask,
+                        uint32_t value, uint32_t lmin, const uint64_t* off, const uint64_t* loff, uint32_t* nbr,
+                        uint64_t* pairs, unsigned long long* qs, hipStream_t s);
+void launch_pairs_swap(uint64_t* p, uint64_t n, hipStream_t s);   // the two words of each pair exchanged
+// p: (slot << 32 | query) in (query, slot) order -> nbr[off[query] + (j - loff[query])] = slot
+void launch_pairs_place(const uint64_t* p, uint64_t n, const uint64_t* off, const uint64_t* loff, uint32_t* nbr,
+                        hipStream_t s);
+void launch_nearest(const World& w, const uint32_t* slots, uint32_t n, const uint32_t* tags, uint32_t mask,
+                    uint32_t value, gw_nearest_rec* out, unsigned long long* qs, hipStream_t s);
+void launch_related(const World& w, const uint32_t* a, const uint32_t* b, uint32_t n, uint8_t* out, hipStream_t s);
+void launch_set_tags(uint32_t* tags, const uint32_t* slots, const uint32_t* vals, uint32_t n, uint32_t cap,
+                     hipStream_t s);
 // ---- decomposed world: owner-side halo routing (halo.hip) -----------------
 constexpr uint8_t SIF_ROUTED = GW_SIF_OWN_CLIENT | GW_SIF_NEIGHBOR_CLIENTS;   // flag bits rows carry
 // the first three words are summed over ranks by gw_world_status
@@ -511,9 +536,9 @@ void launch_wire_encode(const gw_sync_record* rec, uint64_t R, const WirePacket*
                         const uint4* eid, const uint4* cid, uint32_t* out, hipStream_t s);
 void launch_fill_i32(int32_t* p, int32_t v, uint64_t n, hipStream_t s);
 // space lifecycle (space.hip): move a slot range's state, clear a range, count present entities
-void launch_slots_move(const World& w, OpLast* ol, uint4* eid, uint4* cid, uint32_t src, uint32_t dst, uint32_t n,
-                       hipStream_t s);
-void launch_slots_clear(const World& w, OpLast* ol, uint4* eid, uint4* cid, uint32_t base, uint32_t n,
+void launch_slots_move(const World& w, OpLast* ol, uint4* eid, uint4* cid, uint32_t* tags, uint32_t src, uint32_t dst,
+                       uint32_t n, hipStream_t s);
+void launch_slots_clear(const World& w, OpLast* ol, uint4* eid, uint4* cid, uint32_t* tags, uint32_t base, uint32_t n,
                         uint32_t meta, hipStream_t s);
 void launch_count_present(const SlotRec* rec, uint32_t base, uint32_t n, unsigned long long* out, hipStream_t s);
 

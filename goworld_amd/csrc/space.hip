@@ -20,7 +20,8 @@ namespace {
 // zero flags), so its sync bits are set with an OR; the source is cleared by
 // k_slots_clear afterwards (same stream).
 __global__ void __launch_bounds__(NT) k_slots_move(World w, OpLast* __restrict__ ol, uint4* __restrict__ eid,
-                                                    uint4* __restrict__ cid, uint32_t src, uint32_t dst, uint32_t n) {
+                                                    uint4* __restrict__ cid, uint32_t* __restrict__ tags,
+                                                    uint32_t src, uint32_t dst, uint32_t n) {
     const uint32_t i = blockIdx.x * NT + threadIdx.x;
     if (i >= n) return;
     const uint32_t s = src + i, d = dst + i;
@@ -30,14 +31,15 @@ __global__ void __launch_bounds__(NT) k_slots_move(World w, OpLast* __restrict__
     ol[d] = ol[s];
     eid[d] = eid[s];
     cid[d] = cid[s];
+    tags[d] = tags[s];                 // a query tag belongs to the slot (gw_set_tags)
     const uint32_t f = flag_get(w.flags, s);
     if (f) atomicOr(&w.flags[flag_word(d)], f << flag_sh(d));
 }
 
-// slots base + i: absent, in space `meta`, no flags, no client, no ids
+// slots base + i: absent, in space `meta`, no flags, no client, no ids, tag 0
 __global__ void __launch_bounds__(NT) k_slots_clear(World w, OpLast* __restrict__ ol, uint4* __restrict__ eid,
-                                                     uint4* __restrict__ cid, uint32_t base, uint32_t n,
-                                                     uint32_t meta) {
+                                                     uint4* __restrict__ cid, uint32_t* __restrict__ tags,
+                                                     uint32_t base, uint32_t n, uint32_t meta) {
     const uint32_t i = blockIdx.x * NT + threadIdx.x;
     if (i >= n) return;
     const uint32_t s = base + i;
@@ -61,6 +63,7 @@ __global__ void __launch_bounds__(NT) k_slots_clear(World w, OpLast* __restrict_
     ol[s] = z;
     eid[s] = make_uint4(0u, 0u, 0u, 0u);
     cid[s] = make_uint4(0u, 0u, 0u, 0u);
+    tags[s] = 0u;
     if (flag_get(w.flags, s)) atomicAnd(&w.flags[flag_word(s)], ~(3u << flag_sh(s)));
 }
 
@@ -75,14 +78,14 @@ __global__ void __launch_bounds__(NT) k_count_present(const SlotRec* __restrict_
 
 }  // namespace
 
-void launch_slots_move(const World& w, OpLast* ol, uint4* eid, uint4* cid, uint32_t src, uint32_t dst, uint32_t n,
-                       hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_slots_move, dim3(nblk(n, NT)), dim3(NT), 0, s, w, ol, eid, cid, src, dst, n);
+void launch_slots_move(const World& w, OpLast* ol, uint4* eid, uint4* cid, uint32_t* tags, uint32_t src, uint32_t dst,
+                       uint32_t n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_slots_move, dim3(nblk(n, NT)), dim3(NT), 0, s, w, ol, eid, cid, tags, src, dst, n);
 }
 
-void launch_slots_clear(const World& w, OpLast* ol, uint4* eid, uint4* cid, uint32_t base, uint32_t n,
+void launch_slots_clear(const World& w, OpLast* ol, uint4* eid, uint4* cid, uint32_t* tags, uint32_t base, uint32_t n,
                         uint32_t meta, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_slots_clear, dim3(nblk(n, NT)), dim3(NT), 0, s, w, ol, eid, cid, base, n, meta);
+    if (n) hipLaunchKernelGGL(k_slots_clear, dim3(nblk(n, NT)), dim3(NT), 0, s, w, ol, eid, cid, tags, base, n, meta);
 }
 
 void launch_count_present(const SlotRec* rec, uint32_t base, uint32_t n, unsigned long long* out, hipStream_t s) {

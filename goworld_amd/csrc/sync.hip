@@ -13,58 +13,8 @@
 
 namespace gw {
 
-// ---------------------------------------------------------------------------
-// neighbours of a present entity e from the current grid: calls
-// f(rel, w, client) per lane for every candidate (rel: w != e is related to e;
-// client: w's grid-entry bits CLIENT_BIT | gate id < 16, 0 without a client).
-// The window's row ranges are walked flattened, NB_U chunks of 64 in flight.
-// (wave_neighbors_of: e's state a and its space P already loaded)
-template <int NB_U = 4, typename F>
-__device__ __forceinline__ void wave_neighbors_of(const World& w, uint32_t e, const AoiEnt& a, const SpaceP& P, F f) {
-    const float d = P.d;
-    const Win we = win_of(a.x, a.z, d);
-    Rects R;
-    R.n = 1;
-    R.r[0] = search_rect(P, a.x, a.z);
-    Flat fl = flat_build<1>(P, R, w.gn_start, nullptr);
-    unsigned long long se = 0;
-    bool have_se = false;
-    for (uint32_t base = 0; base < fl.total; base += 64u * NB_U) {
-        uint32_t idx[NB_U], kd[NB_U];
-        flat_map_walk<NB_U, 1>(fl, base, idx, kd);
-        GEnt gg[NB_U];
-#pragma unroll
-        for (int u = 0; u < NB_U; ++u) {
-            gg[u].slot = e;
-            if (idx[u] != ~0u) gg[u] = w.gn[idx[u]];
-        }
-#pragma unroll
-        for (int u = 0; u < NB_U; ++u) {
-            if (base + 64u * u >= fl.total) break;            // wave-uniform
-            bool rel = false;
-            const GEnt g = gg[u];
-            if (g.slot != e) {
-                bool ia, near;
-                we.test(g.x, g.z, ia, near);              // B's test of A only in the rounding band
-                rel = ia;
-                if (near) {
-                    const bool ib = in_win(g.x, g.z, d, a.x, a.z);
-                    if (ia != ib) {
-                        if (!have_se) { se = w.rec[e].stamp; have_se = true; }
-                        rel = resolve(ia, ib, se, w.rec[g.slot].stamp);
-                    }
-                }
-            }
-            f(rel, g.slot, g.meta & (CLIENT_BIT | GATE_MASK));
-        }
-    }
-}
-template <int NB_U = 4, typename F>
-__device__ __forceinline__ void wave_neighbors(const World& w, uint32_t e, F f) {
-    const AoiEnt a = w.rec[e].a;
-    if (!(a.meta & PRESENT_BIT)) return;
-    wave_neighbors_of<NB_U>(w, e, a, w.sp[a.meta & SPACE_MASK], f);
-}
+// (the window walk, wave_neighbors / wave_neighbors_of, is in dev_common.hpp:
+// query.hip walks with it too)
 
 // ---------------------------------------------------------------------------
 // flagged entities in slot order, by a one-launch stream compaction (decoupled

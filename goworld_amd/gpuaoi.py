@@ -8,6 +8,9 @@ bench.py.  It mirrors the reference's calls one to one:
   GpuAOI.tick()                 <- OnEnterAOI/OnLeaveAOI fan-out (Entity.go:227-246), batched
   GpuAOI.sync_collect()         <- CollectEntitySyncInfos       (Entity.go:1221-1267)
   GpuAOI.neighbors(slot)        <- Entity.InterestedIn / InterestedBy (Entity.go:53-54)
+  GpuAOI.neighbors_batch(slots) <- the same for many entities at once, as a CSR
+  GpuAOI.nearest(slots, ...)    <- Monster.AI's loop over InterestedIn (unity_demo/Monster.go:48-76)
+  GpuAOI.related(a, b)          <- Entity.IsInterestedIn        (Entity.go:249-251)
 
 There is no CPU fallback: if the HIP library is missing or a call fails, an
 exception is raised (errors map to the reference's gwlog.Panicf on misuse).
@@ -31,9 +34,16 @@ REC_DTYPE = np.dtype([("watcher", "<u4"), ("entity", "<u4"), ("x", "<f4"), ("y",
                       ("z", "<f4"), ("yaw", "<f4")])
 
 FANOUT_DTYPE = np.dtype([("watcher", "<u4"), ("entity", "<u4"), ("item", "<u4")])
+NEAREST_DTYPE = np.dtype([("slot", "<u4"), ("count", "<u4"), ("dist", "<f4"), ("d2", "<f4")])   # gw_nearest_rec
 
 TICK_COPY_TO_HOST, TICK_NO_EVENTS, TICK_DEFER = 1, 2, 4
 MSG_COPY_TO_HOST = 1
+NO_SLOT = 0xFFFFFFFF
+QUERY_COPY_TO_HOST, QUERY_GENERAL_ORDER, QUERY_SLOTS_ON_DEVICE = 1, 2, 4
+# the list lengths at which gw_neighbors_batch changes how it orders a list
+# (gw_internal.hpp QL_WAVE_MAX, QL_LDS_MAX): up to the first in registers, up
+# to the second in LDS, longer by the radix sorts (tests walk across each)
+QUERY_TIER_BOUNDS = (64, 1024)
 SYNC_COPY_TO_HOST, SYNC_BY_CLIENT = 1, 2
 MAX_STAGES = 32
 
@@ -63,6 +73,16 @@ class SyncOut(C.Structure):
 class MsgOut(C.Structure):
     _fields_ = [("rec", C.c_void_p), ("rec_dev", C.c_void_p), ("n_rec", _u64), ("gate_off", C.POINTER(_u64)),
                 ("n_gates", _u32), ("bytes_alg", _u64), ("device_us", _f64)]
+
+
+class NbrOut(C.Structure):
+    _fields_ = [("nbr", C.c_void_p), ("nbr_dev", C.c_void_p), ("off", C.c_void_p), ("off_dev", C.c_void_p),
+                ("n_nbr", _u64), ("n_query", _u32), ("reserved", _u32), ("bytes_alg", _u64), ("device_us", _f64)]
+
+
+class NearOut(C.Structure):
+    _fields_ = [("rec", C.c_void_p), ("rec_dev", C.c_void_p), ("n_query", _u32), ("reserved", _u32),
+                ("bytes_alg", _u64), ("device_us", _f64)]
 
 
 class StageTimes(C.Structure):
@@ -153,6 +173,10 @@ def lib():
         L.gw_halo_status.argtypes = [vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]
         L.gw_client_events.argtypes = [vp, _u32, C.POINTER(MsgOut), C.POINTER(MsgOut)]
         L.gw_fanout.argtypes = [vp, vp, _u32, _u32, C.POINTER(MsgOut)]
+        L.gw_set_tags.argtypes = [vp, vp, vp, _u32]
+        L.gw_neighbors_batch.argtypes = [vp, vp, _u32, _u32, _u32, _u32, C.POINTER(NbrOut)]
+        L.gw_nearest.argtypes = [vp, vp, _u32, _u32, _u32, _u32, C.POINTER(NearOut)]
+        L.gw_related.argtypes = [vp, vp, vp, _u32, vp]
         L.gw_comm_unique_id.argtypes = [vp]
         L.gw_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]
         L.gw_comm_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -191,7 +215,8 @@ EXPORTED = ["gw_abi_version", "gw_init", "gw_shutdown", "gw_last_error", "gw_spa
             "gw_world_submit", "gw_world_status", "gw_set_entity_ids", "gw_clear_entity_ids", "gw_set_client_ids",
             "gw_set_client_syncing", "gw_submit_client_sync", "gw_sync_encode_wire", "gw_space_grow",
             "gw_context_info", "gw_world_far", "gw_world_submit_far", "gw_world_stage_ops",
-            "gw_world_step_host", "gw_comm_init_local", "gw_world_longs", "gw_world_submit_longs"]
+            "gw_world_step_host", "gw_comm_init_local", "gw_world_longs", "gw_world_submit_longs",
+            "gw_set_tags", "gw_neighbors_batch", "gw_nearest", "gw_related"]
 
 
 def comm_init_local(ctxs) -> None:
@@ -473,6 +498,79 @@ class GpuAOI:
         if n.value:
             self._chk(lib().gw_neighbors(self._h, slot, _p(buf), n.value, C.byref(n)))
         return buf
+
+    # ---- batched queries (state of the last flush, like neighbors) ------------
+    def set_tags(self, slots, tags):
+        """gw_set_tags: the 32-bit query tag of each slot (kept across Leave / Enter)."""
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        t = np.ascontiguousarray(tags, dtype=np.uint32)
+        assert len(s) == len(t)
+        self._chk(lib().gw_set_tags(self._h, _p(s), _p(t), len(s)))
+
+    @staticmethod
+    def _query_args(slots, n, copy, general):
+        """(pointer, n, flags, keep-alive) of a query's slots: an array (host) or
+        a device pointer with n (QUERY_SLOTS_ON_DEVICE)."""
+        fl = (QUERY_COPY_TO_HOST if copy else 0) | (QUERY_GENERAL_ORDER if general else 0)
+        if isinstance(slots, (int, np.integer)) and n is not None:
+            return C.c_void_p(int(slots)), int(n), fl | QUERY_SLOTS_ON_DEVICE, None
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        return _p(s), len(s), fl, s
+
+    def neighbors_batch_raw(self, slots, mask: int = 0, value: int = 0, copy: bool = True, general: bool = False,
+                            n: int | None = None) -> NbrOut:
+        """gw_neighbors_batch; the library's gw_nbr_out (pointers valid until the next call)."""
+        o = NbrOut()
+        ptr, cnt, fl, _keep = self._query_args(slots, n, copy, general)
+        self._chk(lib().gw_neighbors_batch(self._h, ptr, cnt, mask, value, fl, C.byref(o)))
+        return o
+
+    def neighbors_batch(self, slots, mask: int = 0, value: int = 0, copy: bool = True, general: bool = False,
+                        n: int | None = None):
+        """InterestedIn of every slots[k] filtered by (tag & mask) == value, as a CSR
+        (off[n + 1] uint64, nbr uint32), each list ascending by slot.  copy=False:
+        the arrays are read back from the device pointers instead of the
+        library's host copy.  slots: an array, or a device pointer with n."""
+        o = self.neighbors_batch_raw(slots, mask, value, copy, general, n)
+        off = np.zeros(o.n_query + 1, np.uint64)
+        nbr = np.zeros(o.n_nbr, np.uint32)
+        if copy:
+            C.memmove(_p(off), o.off, off.nbytes)
+            if o.n_nbr:
+                C.memmove(_p(nbr), o.nbr, nbr.nbytes)
+        else:
+            self.d2h(off, o.off_dev)
+            if o.n_nbr:
+                self.d2h(nbr, o.nbr_dev)
+        return off, nbr
+
+    def nearest_raw(self, slots, mask: int = 0, value: int = 0, copy: bool = True, n: int | None = None) -> NearOut:
+        o = NearOut()
+        ptr, cnt, fl, _keep = self._query_args(slots, n, copy, False)
+        self._chk(lib().gw_nearest(self._h, ptr, cnt, mask, value, fl, C.byref(o)))
+        return o
+
+    def nearest(self, slots, mask: int = 0, value: int = 0, copy: bool = True, n: int | None = None) -> np.ndarray:
+        """gw_nearest: per slots[k] the matching related entity minimising (d2, slot)
+        and the number of matches, NEAREST_DTYPE records (slot NO_SLOT, +inf when
+        nobody matches).  Distance is Entity.DistanceTo in float32, Y included."""
+        o = self.nearest_raw(slots, mask, value, copy, n)
+        r = np.zeros(o.n_query, NEAREST_DTYPE)
+        if o.n_query:
+            if copy:
+                C.memmove(_p(r), o.rec, r.nbytes)
+            else:
+                self.d2h(r, o.rec_dev)
+        return r
+
+    def related(self, a, b) -> np.ndarray:
+        """gw_related: out[i] = a[i] is interested in b[i] (Entity.IsInterestedIn), bool array."""
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        b = np.ascontiguousarray(b, dtype=np.uint32)
+        assert len(a) == len(b)
+        out = np.zeros(len(a), np.uint8)
+        self._chk(lib().gw_related(self._h, _p(a), _p(b), len(a), _p(out)))
+        return out.astype(bool)
 
     def total_neighbors(self) -> int:
         v = _u64()

@@ -25,6 +25,11 @@
  *   gw_sync_collect  <- entity.CollectEntitySyncInfos (Entity.go:1221-1267),
  *                       called from GameService.serveRoutine (GameService.go:186)
  *   gw_set_clients   <- GameClient attach/detach (Entity.client, GameClient.go:14-27)
+ *   gw_neighbors_batch, gw_nearest, gw_related, gw_set_tags
+ *                    <- game logic's reads of the sets per entity per timer,
+ *                       batched: Monster.AI's walk of InterestedIn for the
+ *                       nearest live Player and Monster.Tick's IsInterestedIn
+ *                       (examples/unity_demo/Monster.go:48-98, Entity.go:249-256)
  *
  * Conventions
  *   - Every function returns 0 on success and a negative GW_E* code on error;
@@ -403,6 +408,94 @@ int  gw_fanout(gw_ctx* ctx, const uint32_t* slots, uint32_t n, uint32_t flags, g
 
 /* Total neighbour-list entries held (sum over slots of |InterestedIn|). */
 int  gw_total_neighbors(gw_ctx* ctx, uint64_t* out);
+
+/* ---- batched InterestedIn queries ------------------------------------------
+ * What game logic reads from the sets per entity per timer, for many entities
+ * in one call: examples/unity_demo/Monster.go:48-76 (AI, every 100 ms) walks
+ * InterestedIn for the nearest live Player, Monster.go:78-98 (Tick, every
+ * 30 ms) asks IsInterestedIn(target).
+ *
+ * Visibility: like gw_neighbors, every query sees the state of the last flush
+ * (it settles a deferred tick first); ops submitted but not yet ticked are
+ * invisible.  Pointers in the out structures are owned by the library and stay
+ * valid until the next call of the same entry point.  A query slot that is
+ * absent from every space has an empty set.  Duplicate query slots are
+ * allowed, each gets its own answer.
+ *
+ * Tags: a 32-bit value per slot, opaque to the library, 0 by default (e.g. the
+ * entity's type id in the low bits and an "alive" bit: Monster.AI's TypeName
+ * and hp tests).  A query takes (tag_mask, tag_value): a related entity w
+ * matches when (tag[w] & tag_mask) == tag_value; mask = value = 0 matches
+ * everyone.  A tag belongs to the slot, not to presence: it may be set before
+ * Enter and survives Leave and re-Enter; it follows its slot when
+ * gw_space_grow moves the range and is cleared by gw_space_destroy.  An
+ * out-of-range slot gives GW_ERANGE and nothing is changed; the slots of one
+ * call are distinct (of two tags for one slot either may stay).  In a decomposed
+ * world (gw_world_*) the call sets this rank's copy only (slots are global
+ * ids): a caller that filters by tag there sets the tags on every rank that
+ * holds the entity; tags do not travel through the halo. */
+int  gw_set_tags(gw_ctx* ctx, const uint32_t* slots, const uint32_t* tags, uint32_t n);
+
+#define GW_NO_SLOT             0xffffffffu
+#define GW_QUERY_COPY_TO_HOST  1u
+#define GW_QUERY_GENERAL_ORDER 2u   /* tests: order every list by the general path, whatever its length */
+#define GW_QUERY_SLOTS_ON_DEVICE 4u /* slots is device memory, not validated: an out-of-range slot reads as absent */
+
+/* InterestedIn (== InterestedBy, Entity.go:53-54) of n query slots as a CSR:
+ * list k = nbr[off[k] .. off[k+1]) = {w : w related to slots[k], w matches},
+ * ascending by slot (ordered on the device; with mask = value = 0 it equals
+ * gw_neighbors(slots[k])).  n == 0 is valid: off = {0}.  A host slot at or
+ * beyond the context's slots gives GW_ERANGE and no output.  bytes_alg: 16 B
+ * per candidate walked (both passes), 4 B per list entry, 8 B per offset, 4 B
+ * per query slot. */
+typedef struct gw_nbr_out {
+    const uint32_t* nbr;          /* host (GW_QUERY_COPY_TO_HOST), else NULL    */
+    const uint32_t* nbr_dev;      /* device: n_nbr slots                        */
+    const uint64_t* off;          /* host (GW_QUERY_COPY_TO_HOST), else NULL    */
+    const uint64_t* off_dev;      /* device: n_query + 1 offsets                */
+    uint64_t n_nbr;
+    uint32_t n_query, reserved;
+    uint64_t bytes_alg;
+    double   device_us;
+} gw_nbr_out;
+int  gw_neighbors_batch(gw_ctx* ctx, const uint32_t* slots, uint32_t n, uint32_t tag_mask, uint32_t tag_value,
+                        uint32_t flags, gw_nbr_out* out);
+
+/* Monster.AI's loop (Monster.go:48-76) for n query slots in one launch: per
+ * slot the matching related entity nearest to it, and how many match.
+ * Distance is Entity.DistanceTo (Entity.go:254-256 -> Vector3.DistanceTo,
+ * Vector3.go:23-28) bit for bit: float32 differences of the two Positions as
+ * of the last flush (x, y, z: Y counts here although it does not count in
+ * AOI), d2 = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)) without fused
+ * multiply-add, dist = float32(sqrt(float64(d2))).
+ * The choice minimises (d2, slot).  Among candidates of equal d2 the reference
+ * keeps whichever Go's map iteration met first (Monster.go:61, strict >), so
+ * any fixed rule is one of its outcomes; this one is the lowest slot.
+ * bytes_alg: 16 B per candidate walked, 64 B per matching related entity,
+ * 16 B per record, 4 B per query slot. */
+typedef struct gw_nearest_rec {   /* 16 B */
+    uint32_t slot;        /* the chosen entity, GW_NO_SLOT when nobody matches    */
+    uint32_t count;       /* matching related entities (|filtered InterestedIn|)  */
+    float    dist;        /* Entity.DistanceTo of the chosen one; +inf when none  */
+    float    d2;          /* its squared distance as computed above; +inf when none */
+} gw_nearest_rec;
+typedef struct gw_near_out {
+    const gw_nearest_rec* rec;        /* host (GW_QUERY_COPY_TO_HOST), else NULL */
+    const gw_nearest_rec* rec_dev;    /* device: n_query records                 */
+    uint32_t n_query, reserved;
+    uint64_t bytes_alg;
+    double   device_us;
+} gw_near_out;
+int  gw_nearest(gw_ctx* ctx, const uint32_t* slots, uint32_t n, uint32_t tag_mask, uint32_t tag_value,
+                uint32_t flags, gw_near_out* out);
+
+/* Entity.IsInterestedIn (Entity.go:249-251; Monster.go:79,89) for n pairs:
+ * out[i] = 1 iff a[i] is interested in b[i] as of the last flush, i.e. both
+ * are present in the same space, a[i] != b[i], and the pair is related (each
+ * inside the other's window; in the rounding band of the window edge the
+ * member with the later AOI op decides, as everywhere).  a, b and out are host
+ * memory; an out-of-range slot gives GW_ERANGE. */
+int  gw_related(gw_ctx* ctx, const uint32_t* a, const uint32_t* b, uint32_t n, uint8_t* out);
 
 /* Device pointer helpers for device-resident benchmarking. */
 int  gw_device_alloc(gw_ctx* ctx, size_t bytes, void** dev_ptr);
